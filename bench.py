@@ -1,8 +1,18 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: voxel-timesteps/sec of a batch of random 10x10x10 soft robots (BASELINE.json).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A PLAIN run does what the headline figure needs and nothing else: it builds the population, pre-advances and warms up, times the K
+steps, gathers the fitness records, writes its outputs if --dump-outputs is given and prints the line.  Every other measurement
+described below -- `strong` and `multi_handle` (N > 1), `other_configs` and `cpu_baseline` with its live parity check (N = 1) -- is
+made only with --full (--no-other-configs / --no-cpu-baseline then leave one of the two out); the fields of the line that read
+committed profiles (`parity`, `roofline.traffic` / `compute` / `binding`) cost no run and stay.
+
+--dump-outputs DIR: after the timed steps, the state of every voxel and the result record of every robot the timed call stepped
+(rank 0's population) as DIR/state.npy, records.npy, robots.npy in float64 (dump_outputs below).  The population is a function of the
+arguments alone, so two builds run with the same arguments can be compared output for output.
 
 Workload of the headline `value` = BASELINE.json configs[2], "population 512 of 10x10x10 robots": it fits one MI355X, so
 a single GPU steps the whole population of 512; with N GPUs every rank steps its own 512 robots (WEAK scaling, seeds
@@ -14,7 +24,7 @@ actuation on, bonds in both the small- and the large-angle branch (`config.large
 of the timed window).  After the timed region the fitness records of all ranks are gathered with one RCCL all_gather
 (the path's only collective).
 
-With N > 1 the same line carries `strong`: BASELINE configs[2] as stated -- ONE population of 512, partitioned over the
+With N > 1 and --full the same line carries `strong`: BASELINE configs[2] as stated -- ONE population of 512, partitioned over the
 N ranks by cost (64 per GPU at N = 8) -- timed the same way right after the weak run.  At N = 1 the same statement is measured as
 far as one GPU can (round 6): `other_configs` carries shard 0 of the 8 cost-balanced shards -- the 64 robots ONE of eight GPUs would
 step -- with the default kernels and with tile_small, and the projected 8-GPU strong rate; `--shard-of K` times that shard as the
@@ -46,10 +56,10 @@ The JSON line also carries
                 with the SQ_INSTS_VALU_*_F64 counters (profiles/r*_flops_per_unit.json, scripts/flops_per_unit.sh) -- times this run's own
                 voxel-steps/s over its HIP-event time, against the 78.6 TFLOP/s vector-FP64 peak; every other_configs entry carries its own.
   ranks         N > 1: world size, backend, and per rank the device (index, PCI bus id) and its ms per step, gathered over the RCCL group
-  other_configs the other BASELINE configs at their stated sizes (64 x 6^3 walkers, 64 x 8^3 swimmers, one 20^3 lattice), 512 dense 10^3,
+  other_configs (--full) the other BASELINE configs at their stated sizes (64 x 6^3 walkers, 64 x 8^3 swimmers, one 20^3 lattice), 512 dense 10^3,
                 a mixed generation run to completion, and configs[2] as stated (one of 8 shards); N = 1 only: value, us per step,
                 algorithmic roofline fraction, binding, kernel
-  cpu_baseline  the reference C++ voxelyze (oracle/_ref/voxelyze_ref, built from the reference sources) on this box's host
+  cpu_baseline  (--full) the reference C++ voxelyze (oracle/_ref/voxelyze_ref, built from the reference sources) on this box's host
                 cores: `nproc` concurrent processes on 2 x nproc robots of the bench population (evaluation.py:89 launches
                 one process per robot and lets the OS schedule them), plus the single-process figure, plus the single-process figure of the
                 build the reference SHIPS (-O0 library objects; the others are -O3); rank 0, N = 1 only.
@@ -394,6 +404,33 @@ def timed_steps(eng, steps, barrier=None):
     return eng.counters().kernel_seconds - k0, host
 
 
+DUMP_BYTES_MAX = 48 << 20      # --dump-outputs writes at most this much (the whole headline population: 40 MB of state)
+
+
+def dump_outputs(out_dir, eng, records):
+    """--dump-outputs DIR: what a caller of the timed path holds after its last step, as float64 .npy files, so that two builds can be
+    compared output for output (the population is a function of the arguments alone: seeded robots, the same step counts):
+      state.npy    [voxels, 14] vxh_get_state of the dumped robots, one robot after the other in robot order
+      records.npy  [robots, RECORD_LEN] their result records (evosoro_amd/parallel.py RECORD_FIELDS) as the fitness gather sends them
+      robots.npy   [robots] which robots of this rank's population those are: all of them while the files stay within DUMP_BYTES_MAX,
+                   else a fixed (seeded) sample of whole robots
+    Read back from the engine outside every timed region; rank 0's population only."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(records)
+    per_robot = [eng.dims(i)["nvox"] * 14 * 8 + records.shape[1] * 8 + 8 for i in range(n)]
+    picked, used = [], 0
+    for i in np.random.RandomState(1234).permutation(n):
+        if used + per_robot[i] <= DUMP_BYTES_MAX:
+            picked.append(int(i))
+            used += per_robot[i]
+    picked.sort()
+    state = np.concatenate([eng.state(i) for i in picked]) if picked else np.zeros((0, 14))
+    np.save(os.path.join(out_dir, "state.npy"), np.ascontiguousarray(state, dtype=np.float64))
+    np.save(os.path.join(out_dir, "records.npy"), np.ascontiguousarray(records[picked], dtype=np.float64))
+    np.save(os.path.join(out_dir, "robots.npy"), np.array(picked, dtype=np.float64))
+
+
 def side_config(engine, name, variant, count, shape, env, device, steps, full=False, phase=False, init_time=0.02, key=None, options=None):
     """one of the other BASELINE configs at its stated size: pre-advanced past InitCmTime, then `steps` timed steps"""
     from evosoro_amd import workloads
@@ -578,8 +615,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--robots-per-gpu", type=int, default=512)
     ap.add_argument("--lattice", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: other_configs and cpu_baseline (N = 1), the strong and one-handle legs (N > 1); a plain run has none of them")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: leave out other_configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they computed -- state and result record of every robot of rank 0 -- as DIR/<name>.npy (float64)")
     ap.add_argument("--shard-of", type=int, default=0, metavar="K",
                     help="time shard 0 of K (greedy LPT by voxels) of the population instead of the whole of it: BASELINE configs[2] as one of K GPUs sees it")
     args = ap.parse_args()
@@ -717,10 +758,12 @@ def main():
                                         torch.device("cuda", local_rank) if (distributed and not share_gpu) else None)
         gather_ms = (time.perf_counter() - tg) * 1e3
         assert table.shape[0] == world * n_local and (table[:, 2] > 0).all()
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, eng, records)
         eng.close()
 
         strong = None
-        if world > 1:
+        if world > 1 and args.full:
             # BASELINE configs[2] as stated: ONE population of 512, partitioned over the ranks by cost (LPT on voxels x steps)
             shared = [make_population(os.path.join(tmp, "strong"), n_local, 0, shape, sim_time, INIT_CM_TIME) if rank == 0 else None]
             dist.broadcast_object_list(shared, src=0, group=ctl)   # (one node: rank 0's files are visible to every rank)
@@ -744,7 +787,7 @@ def main():
             teng.close()
 
         handle = None
-        if world > 1:
+        if world > 1 and args.full:
             # the other N-GPU route: ONE process, one handle over the N devices (vxh_create_multi: the C ABI partitions the population
             # by cost, one host thread per device, results stay in host memory -- no collective).  Rank 0 steps N x 512 robots through
             # it while the other ranks wait at the HOST-side barrier below (their engines are closed, their GPUs idle: a rank
@@ -841,7 +884,7 @@ def main():
             if bind:
                 out["roofline"]["binding"] = bind          # (per GPU: this rank's population over the slowest rank's time)
                 out["roofline"]["bound"] = "fp64-issue"
-            if world == 1 and not args.no_other_configs:
+            if args.full and world == 1 and not args.no_other_configs:
                 out["other_configs"] = [
                     side_workload(engine, "cfg1", local_rank), side_workload(engine, "cfg3", local_rank), side_workload(engine, "cfg4", local_rank),
                     side_workload(engine, "dense", local_rank), side_workload(engine, "mixed", local_rank),
@@ -850,7 +893,7 @@ def main():
                     out["other_configs"].append(shard_of_population(engine, all_local_paths, local_rank, 8, 1024))
                 for entry in out["other_configs"]:
                     entry.pop("_voxel_steps_process", None)
-            if world == 1 and not args.no_cpu_baseline:
+            if args.full and world == 1 and not args.no_cpu_baseline:
                 out["cpu_baseline"] = cpu_baseline(shape, local_rank)
                 check = out["cpu_baseline"].pop("parity_check", None)
                 if check:

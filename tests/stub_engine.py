@@ -133,6 +133,9 @@ class Engine(object):
     def result(self, i):
         return _Result(self.sims[i].result(), self.sims[i].info().col_rebuilds)
 
+    def state(self, i):
+        return self.sims[i].state()
+
     def fitness_file_name(self, i):
         return self.models[i]["fitness_file_name"]
 

@@ -7,7 +7,8 @@ import sys
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--steps", "6", "--warmup", "2", "--robots-per-gpu", "3", "--lattice", "4", "--no-cpu-baseline", "--no-other-configs"]
+# (--full: the strong and one-handle legs of an N > 1 run are measured only then; the N = 1 legs it would add are switched off)
+SMALL = ["--steps", "6", "--warmup", "2", "--robots-per-gpu", "3", "--lattice", "4", "--full", "--no-cpu-baseline", "--no-other-configs"]
 
 
 def _run(cmd, env_extra, timeout=600):
@@ -101,11 +102,90 @@ def test_world_size_mismatch_fails_loudly():
     assert proc.returncode != 0 and "WORLD_SIZE 2" in proc.stderr.decode()
 
 
+PLAIN = ["--gpus", "1", "--steps", "6", "--warmup", "2", "--robots-per-gpu", "3", "--lattice", "4"]
+
+
+def _check_dump(out, where):
+    """the files of --dump-outputs against the line of the run that wrote them"""
+    import numpy as np
+    from evosoro_amd import parallel
+    got = {n: np.load(os.path.join(where, n + ".npy")) for n in ("state", "records", "robots")}
+    assert sorted(os.listdir(where)) == ["records.npy", "robots.npy", "state.npy"]
+    assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in got.values())
+    n = out["config"]["robots_per_gpu"]
+    assert got["robots"].tolist() == list(range(n))                      # (a population this small is dumped whole)
+    assert got["state"].shape == (out["config"]["voxels_per_gpu"], 14) and got["records"].shape == (n, parallel.RECORD_LEN)
+    assert got["records"][:, parallel.RECORD_FIELDS.index("nvox")].sum() == out["config"]["voxels_per_gpu"]
+    # --steps really is the number of timed steps: every robot has taken the untimed steps the line states plus exactly those
+    assert (got["records"][:, parallel.RECORD_FIELDS.index("steps")] == out["config"]["pre_advanced_steps"] + out["steps"]).all()
+    return got
+
+
+def test_a_plain_run_measures_the_headline_only_and_dumps_what_it_computed_on_the_stub(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W`: the line carries the headline fields and none of the legs behind --full; with
+    --dump-outputs the state and the records of the population are written, and a second run with the same arguments writes the same."""
+    import numpy as np
+    runs = []
+    for name in ("a", "b"):
+        proc = _run([sys.executable, os.path.join(REPO, "tests", "bench_stub_runner.py")] + PLAIN + ["--dump-outputs", str(tmp_path / name)], {})
+        assert proc.returncode == 0, proc.stderr.decode()[-3000:]
+        out = _line(proc)
+        assert out["metric"] == "voxel_timesteps_per_sec" and out["unit"] == "voxel-timesteps/s" and out["higher_is_better"] is True
+        assert out["dtype"] == "f64" and out["steps"] == 6 and out["warmup"] == 2 and out["n_gpus"] == 1
+        assert out["ms_per_step"] > 0 and out["value"] == pytest.approx(out["config"]["voxels_per_gpu"] / (out["ms_per_step"] * 1e-3), rel=1e-9)
+        assert not set(out) & {"other_configs", "cpu_baseline", "strong", "multi_handle"}
+        runs.append(_check_dump(out, str(tmp_path / name)))
+    for n in runs[0]:
+        assert np.array_equal(runs[0][n], runs[1][n]), n
+
+
+def test_a_large_population_is_dumped_as_a_fixed_sample_of_whole_robots(tmp_path, monkeypatch):
+    """dump_outputs over its byte limit: the same robots every time, whole, in robot order, and the files within the limit"""
+    import numpy as np
+    sys.path.insert(0, REPO)
+    try:
+        import bench
+    finally:
+        sys.path.remove(REPO)
+
+    class Eng(object):
+        def dims(self, i):
+            return {"nvox": 10 + i}
+
+        def state(self, i):
+            return np.full((10 + i, 14), float(i))
+    records = np.arange(40 * 35, dtype=np.float64).reshape(40, 35)
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 40000)
+    picks = []
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), Eng(), records)
+        got = {n: np.load(str(tmp_path / name / (n + ".npy"))) for n in ("state", "records", "robots")}
+        picked = got["robots"].astype(int)
+        assert 0 < len(picked) < 40 and list(picked) == sorted(set(picked))
+        assert sum(a.nbytes for a in got.values()) <= 40000
+        assert np.array_equal(got["records"], records[picked])
+        assert np.array_equal(got["state"][:, 0], np.concatenate([np.full(10 + i, float(i)) for i in picked]))
+        picks.append(list(picked))
+    assert picks[0] == picks[1]
+
+
+@pytest.mark.gpu
+def test_a_plain_run_with_the_real_engine_dumps_its_outputs(tmp_path):
+    """the same on the GPU: the plain command on a small population, its line and its files"""
+    proc = _run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--robots-per-gpu", "16",
+                 "--lattice", "6", "--dump-outputs", str(tmp_path / "out")], {})
+    assert proc.returncode == 0, proc.stderr.decode()[-3000:]
+    out = _line(proc)
+    assert out["steps"] == 20 and out["ms_per_step"] > 0 and out["value"] > 0 and out["clock"] == "hip_event"
+    assert not set(out) & {"other_configs", "cpu_baseline", "strong", "multi_handle"}
+    _check_dump(out, str(tmp_path / "out"))
+
+
 @pytest.mark.gpu
 def test_gpus_2_on_one_device_with_the_real_engine():
     """the same on the GPU box: two ranks sharing device 0 (gloo), the real library"""
     proc = _run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--robots-per-gpu", "16",
-                 "--lattice", "6", "--no-cpu-baseline", "--no-other-configs"], {"VXH_BENCH_SHARE_GPU": "1"})
+                 "--lattice", "6", "--full", "--no-cpu-baseline", "--no-other-configs"], {"VXH_BENCH_SHARE_GPU": "1"})
     assert proc.returncode == 0, proc.stderr.decode()[-3000:]
     out = _line(proc)
     assert out["n_gpus"] == 2 and out["config"]["robots_per_gpu"] == 16 and out["value"] > 0
@@ -141,13 +221,13 @@ def test_the_bench_lines_live_parity_check(tmp_path):
     ref = os.path.join(REPO, "oracle", "_ref", "voxelyze_ref")
     if not os.path.exists(ref):
         pytest.skip("oracle/_ref is not built")
-    sys.path.insert(0, REPO)
-    try:
-        import bench
-    finally:
-        sys.path.remove(REPO)
-    paths = bench.make_population(str(tmp_path), 6, 40, (6, 6, 6), 0.06, 0.02)
-    bench.run_reference(ref, paths, str(tmp_path), 6)
-    check = bench.live_parity(paths, str(tmp_path), 0)
+    # in a process of its own: the test runner must not hold the GPU open itself -- tests/test_cli_broker.py, next in line, starts
+    # sixteen processes that each do, and sixteen is as many as may share one device
+    code = ("import json, sys; sys.path.insert(0, %r); import bench; "
+            "paths = bench.make_population(%r, 6, 40, (6, 6, 6), 0.06, 0.02); bench.run_reference(%r, paths, %r, 6); "
+            "print(json.dumps(bench.live_parity(paths, %r, 0)))" % (REPO, str(tmp_path), ref, str(tmp_path), str(tmp_path)))
+    proc = _run([sys.executable, "-c", code], {})
+    assert proc.returncode == 0, proc.stderr.decode()[-3000:]
+    check = _line(proc)
     assert check["live"] and check["robots"] == 6 and check["numeric_tags_per_file"] >= 10
     assert check["result_files_byte_identical"] == 6 and check["worst_tag_difference"] == 0.0, check

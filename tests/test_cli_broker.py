@@ -11,8 +11,10 @@ configs[4] (the tiled kernel), every result XML checked against the reference bi
 through the broker; wall clocks written to gpurun_out/r04_concurrent_cli.json."""
 import json
 import os
+import shutil
 import subprocess
 import sys
+import tempfile
 import time
 
 import pytest
@@ -23,8 +25,27 @@ from oracle import vxoracle as vo
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _env(tmp_path, **extra):
-    env = dict(os.environ, VXH_BROKER_SOCKET=str(tmp_path / "broker.sock"), VXH_BROKER_IDLE_S="3", VXH_BROKER_LOG=str(tmp_path / "broker.log"))
+SUN_PATH_MAX = 107          # characters of a unix socket's name (sockaddr_un.sun_path less its terminator)
+
+
+@pytest.fixture
+def sock_dir(tmp_path):
+    """Where the test's broker listens: pytest's tmp_path when `broker.sock` in it fits a socket's name, else a fresh directory of the
+    user's own right under /tmp (where the command line's default socket lives too) -- under a deep TMPDIR tmp_path does not fit, the
+    broker refuses the name ("socket path too long") and every client falls back to stepping its file itself."""
+    if len(str(tmp_path / "broker.sock")) <= SUN_PATH_MAX:
+        yield tmp_path
+        return
+    short = tempfile.mkdtemp(prefix="vxb-", dir="/tmp")
+    assert len(os.path.join(short, "broker.sock")) <= SUN_PATH_MAX
+    try:
+        yield short
+    finally:
+        shutil.rmtree(short, ignore_errors=True)
+
+
+def _env(tmp_path, sock_dir, **extra):
+    env = dict(os.environ, VXH_BROKER_SOCKET=os.path.join(str(sock_dir), "broker.sock"), VXH_BROKER_IDLE_S="3", VXH_BROKER_LOG=str(tmp_path / "broker.log"))
     env.pop("VXH_BROKER", None)
     env.update(extra)
     return env
@@ -35,12 +56,12 @@ def _stat(env):
     return out.strip()
 
 
-def test_broker_plumbing_without_a_gpu(golden_dir, tmp_path):
+def test_broker_plumbing_without_a_gpu(golden_dir, tmp_path, sock_dir):
     import torch
     if torch.cuda.is_available():
         pytest.skip("a GPU is present: the GPU test below covers the broker")
     eng_mod.build()
-    env = _env(tmp_path)
+    env = _env(tmp_path, sock_dir)
     vxa = os.path.join(golden_dir, "vxa", "soft5_init0.vxa")
     procs = [subprocess.Popen([eng_mod.CLI_PATH, "-f", vxa], env=env, cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.PIPE) for _ in range(6)]
     outs = [p.communicate(timeout=60) for p in procs]
@@ -98,18 +119,18 @@ def _check_results(golden_dir, work, cases=CASES):
 
 
 @pytest.mark.gpu
-def test_sixteen_concurrent_voxelyze_processes(golden_dir, tmp_path, kernel_path):
+def test_sixteen_concurrent_voxelyze_processes(golden_dir, tmp_path, sock_dir, kernel_path):
     if kernel_path != "auto":
         pytest.skip("the command line with the engine's own kernel choice (the lattice above 1024 voxels needs its own tile count)")
     record = {"cases": CASES, "note": "16 concurrent `voxelyze -f x.vxa` processes started the way evosoro/tools/evaluation.py:89-90 starts them; "
                                       "wall clock from the first Popen to the last exit; every result XML checked against the reference binary's"}
     # (a) every process steps its own robot: 16 HIP contexts on one GPU
-    wall, codes, errs = _generation(golden_dir, str(tmp_path / "direct"), _env(tmp_path, VXH_BROKER="0"))
+    wall, codes, errs = _generation(golden_dir, str(tmp_path / "direct"), _env(tmp_path, sock_dir, VXH_BROKER="0"))
     assert codes == [1] * len(CASES), [e.decode()[-300:] for e in errs if e]
     _check_results(golden_dir, str(tmp_path / "direct"))
     record["direct"] = {"wall_s": wall, "tile_timeouts_recovered": sum(1 for e in errs if b"stepped again without the tiled kernel" in e)}
     # (b) through the broker: the first client starts it; a second generation right behind finds it running (HIP runtime warm)
-    env = _env(tmp_path)
+    env = _env(tmp_path, sock_dir)
     wall1, codes, errs = _generation(golden_dir, str(tmp_path / "broker1"), env)
     assert codes == [1] * len(CASES), [e.decode()[-300:] for e in errs if e]
     _check_results(golden_dir, str(tmp_path / "broker1"))

@@ -30,9 +30,7 @@ enum RobotFlags { RF_SELF_COL = 1, RF_GRAV = 2, RF_FLOOR = 4, RF_TEMP = 8, RF_ST
 
 enum { VXH_ORDER_MAX_STEPS = 128,    // launches of at most this many steps are dispatched "robots due for a broad-phase run first" (kernels_fused.hpp)
        VXH_ORDER_HORIZON = 32 };     // ... and what a longer launch calls "due" when it leaves the flags for the launch behind it
-enum { VXH_RIMG_CAP = 2048 };
-// pair kernel (kernels_pair.hpp; compiled with -DVXH_PAIR only: the developer library): threads, voxel slots, wavefronts, voxel wavefronts
-enum { VXH_PAIR_T = 512, VXH_PAIR_NV = 1024, VXH_PAIR_NW = 8, VXH_PAIR_NVW = 16 };     // entries of a saved contact-row image (the LDS pool holds at most 24 KB / 12 B)
+enum { VXH_RIMG_CAP = 2048 };        // entries of a saved contact-row image (the LDS pool holds at most 24 KB / 12 B)
 
 struct DRobot {               // constant per robot
     int vox_begin, nvox, surf_begin, nsurf, flags, stop_type, excl_wpr;

@@ -43,7 +43,6 @@ struct Engine::Device {
         int block = 0, nacc = 0, fluid = 0, tabg = 0;   // template arguments of k_robot_steps
         int wide = 0;                     // 1: k_robot_wide<block, fluid, tabg> (kernels_wide.hpp)
         int two_tiles = 0;                // wide kernel: a second pose tile in LDS (two barriers per step instead of three)
-        int pair = 0;                     // 1: k_robot_pair<tabg, sel> (kernels_pair.hpp; block = 512 threads, 1024 voxel slots); 2: its SEL form
         int count = 0;
         const int* list = nullptr;
         // dispatch order of short launches (kernels_fused.hpp fused_dispatch_slot): one bit per list entry, written by a launch for the next
@@ -255,7 +254,7 @@ int Engine::append(std::vector<RobotModel>&& built)
 std::vector<RobotModel> Engine::build_vxa(const char* data, size_t len) const
 {
     VxaModel vxa = read_vxa(data, len, variant_);
-    if (shape_descriptors_) vxa.want_mesh = true;
+    if (opt_.shape_descriptors) vxa.want_mesh = true;
     if (!vxa.unsupported.empty()) {
         std::string msg = "unsupported .vxa feature(s):";
         for (const auto& u : vxa.unsupported) msg += " [" + u + "]";
@@ -289,7 +288,7 @@ std::vector<RobotModel> Engine::build_vxa_files(const std::vector<std::string>& 
                 ss << in.rdbuf();
                 const std::string text = ss.str();
                 VxaModel vxa = read_vxa(text.data(), text.size(), variant_);
-                if (shape_descriptors_) vxa.want_mesh = true;
+                if (opt_.shape_descriptors) vxa.want_mesh = true;
                 if (!vxa.unsupported.empty()) {
                     std::string msg = "unsupported .vxa feature(s):";
                     for (const auto& u : vxa.unsupported) msg += " [" + u + "]";
@@ -345,7 +344,7 @@ std::vector<RobotModel> Engine::build_models(std::vector<VxaModel>&& models) con
 std::vector<VxaModel> Engine::models_from_arrays(const char* template_vxa, size_t len, const vxh_robot_arrays* in, int n, bool round_like_text) const
 {
     VxaModel base = read_vxa(template_vxa, len, variant_);
-    if (shape_descriptors_) base.want_mesh = true;
+    if (opt_.shape_descriptors) base.want_mesh = true;
     if (!base.unsupported.empty()) {
         std::string msg = "unsupported .vxa feature(s):";
         for (const auto& u : base.unsupported) msg += " [" + u + "]";
@@ -520,6 +519,43 @@ void Engine::drop_graph()
     if (dev_->graph) { hipGraphDestroy(dev_->graph); dev_->graph = nullptr; }
 }
 
+// The options of vxh_set_option, each described once.  A FLAG is stored as value != 0, an INT truncated.  Accepted values: ANY, the WHOLE
+// numbers lo..hi, or the RANGE lo <= value <= hi.  `batch`: which kernel steps a robot, its tiling and the size of its contact rows are
+// part of the uploaded batch -- set before the first vxh_run / vxh_step, or right after vxh_reset (no step taken yet: the batch is then
+// assembled again at the next run); an unchanged value is always fine, nothing would be assembled again.  (`fused` too, since round 5:
+// the resident kernels keep the bond history in their own array and a saved image of the contact rows, so a robot that changed kernels
+// in the middle of a run would read stale history -- ADVICE round 4.)  `graph`: the captured step graph depends on it (drop_graph).
+namespace {
+struct OptionDesc {
+    const char* name;
+    int Options::*member;
+    enum Kind { FLAG, INT } kind;
+    enum Accept { ANY, WHOLE, RANGE } accept;
+    double lo, hi;
+    bool batch, graph;
+    int coerce(double value) const { return kind == FLAG ? (int)(value != 0) : (int)value; }
+    bool accepts(double value) const { return accept == ANY || (value >= lo && value <= hi && (accept == RANGE || value == std::trunc(value))); }
+};
+const OptionDesc option_table[] = {
+    {"tiled",             &Options::tiled,             OptionDesc::INT,  OptionDesc::WHOLE, 0, 2,      true,  false},
+    {"tiles_per_robot",   &Options::tiles_per_robot,   OptionDesc::INT,  OptionDesc::RANGE, 0, 4096,   true,  false},
+    {"tile_small",        &Options::tile_small,        OptionDesc::FLAG, OptionDesc::WHOLE, 0, 1,      true,  false},
+    {"wide",              &Options::wide,              OptionDesc::FLAG, OptionDesc::WHOLE, 0, 1,      true,  false},
+    {"wide_two_tiles",    &Options::wide_two_tiles,    OptionDesc::FLAG, OptionDesc::WHOLE, 0, 1,      true,  false},
+    {"col_cap",           &Options::col_cap,           OptionDesc::INT,  OptionDesc::RANGE, 0, 1e6,    true,  false},
+    {"fused",             &Options::fused,             OptionDesc::FLAG, OptionDesc::WHOLE, 0, 1,      true,  true},
+    {"steps_per_launch",  &Options::steps_per_launch,  OptionDesc::INT,  OptionDesc::RANGE, 1, 200000, false, false},
+    {"graph_steps",       &Options::graph_steps,       OptionDesc::INT,  OptionDesc::RANGE, 0, 1e6,    false, true},
+    {"shape_descriptors", &Options::shape_descriptors, OptionDesc::FLAG, OptionDesc::WHOLE, 0, 1,      false, false},      // (robots added FROM NOW ON carry the surface mesh)
+    {"host_results",      &Options::host_results,      OptionDesc::FLAG, OptionDesc::ANY,   0, 0,      false, false},
+};
+const OptionDesc& find_option(const std::string& key)
+{
+    for (const OptionDesc& d : option_table) if (key == d.name) return d;
+    throw std::invalid_argument("unknown option " + key);
+}
+}  // namespace
+
 // throws what set_option would throw for this key / value in the engine's present state, and changes nothing: a handle over several
 // devices applies an option to all of its engines or to none
 void Engine::check_option(const std::string& key, double value) const
@@ -527,35 +563,14 @@ void Engine::check_option(const std::string& key, double value) const
 #ifdef VXH_PHASE_TIMING
     if (key == "dbg") return;                 // physics-skipping what-if switches: developer library only
 #endif
-    if (key == "host_results") return;
-    if (key == "shape_descriptors") { if (value != 0 && value != 1) throw std::invalid_argument("shape_descriptors: 0 or 1"); return; }
-    if (key == "steps_per_launch") { if (!(value >= 1 && value <= 200000)) throw std::invalid_argument("steps_per_launch out of range"); return; }
-    if (key == "graph_steps") { if (!(value >= 0 && value <= 1e6)) throw std::invalid_argument("graph_steps out of range"); return; }
-    if (key == "tiled" || key == "tiles_per_robot" || key == "tile_small" || key == "wide" || key == "wide_two_tiles" || key == "col_cap" || key == "fused" || key == "pair" || key == "pair_sel") {
-        // which kernel steps a robot, its tiling and the size of its contact rows are part of the uploaded batch: set before the first
-        // vxh_run / vxh_step, or right after vxh_reset (no step taken yet: the batch is then assembled again at the next run)
-        {   // (an unchanged value is always fine: nothing would be assembled again)
-            const double now = key == "wide" ? (double)wide_ : key == "wide_two_tiles" ? (double)wide_two_tiles_ : key == "col_cap" ? (double)col_cap_ :
-                               key == "tiled" ? (double)tiled_ : key == "tile_small" ? (double)tile_small_ : key == "fused" ? (double)fused_ :
-                               key == "pair" ? (double)pair_ : key == "pair_sel" ? (double)pair_sel_ : (double)tiles_per_robot_;
-            const bool flag = key == "wide" || key == "wide_two_tiles" || key == "tile_small" || key == "fused" || key == "pair_sel";
-            if (prepared_ && rounds_done_ > 0 && now != (flag ? (double)(value != 0) : (double)(int)value))
-                throw std::logic_error("option " + key + " must be set before the first vxh_run/vxh_step (or right after vxh_reset)");
-        }
-        // (`fused` too, since round 5: the resident kernels keep the bond history in their own array and a saved image of the contact rows, so
-        // a robot that changed kernels in the middle of a run would read stale history -- ADVICE round 4)
-        if ((key == "wide" || key == "wide_two_tiles" || key == "fused" || key == "pair_sel") && value != 0 && value != 1) throw std::invalid_argument(key + ": 0 or 1");
-        if (key == "pair" && value != 0 && value != 1 && value != 2) throw std::invalid_argument("pair: 0, 1 or 2");
-#ifndef VXH_PAIR
-        if (key == "pair" && value != 0) throw std::invalid_argument("pair: k_robot_pair is compiled into the developer library only (make -C evosoro_amd/csrc prof: -DVXH_PAIR)");
-#endif
-        if (key == "col_cap" && !(value >= 0 && value <= 1e6)) throw std::invalid_argument("col_cap out of range");
-        if (key == "tiled" && value != 0 && value != 1 && value != 2) throw std::invalid_argument("tiled: 0, 1 or 2");
-        if (key == "tile_small" && value != 0 && value != 1) throw std::invalid_argument("tile_small: 0 or 1");
-        if (key == "tiles_per_robot" && !(value >= 0 && value <= 4096)) throw std::invalid_argument("tiles_per_robot out of range");
-        return;
+    const OptionDesc& d = find_option(key);
+    if (d.batch && prepared_ && rounds_done_ > 0 && opt_.*d.member != d.coerce(value))      // (the state of the batch is judged before the value)
+        throw std::logic_error("option " + key + " must be set before the first vxh_run/vxh_step (or right after vxh_reset)");
+    if (!d.accepts(value)) {
+        char want[64];
+        std::snprintf(want, sizeof(want), d.accept == OptionDesc::WHOLE ? ": a whole number from %g to %g" : ": %g to %g", d.lo, d.hi);
+        throw std::invalid_argument(key + want);
     }
-    throw std::invalid_argument("unknown option " + key);
 }
 
 void Engine::set_option(const std::string& key, double value)
@@ -564,27 +579,15 @@ void Engine::set_option(const std::string& key, double value)
 #ifdef VXH_PHASE_TIMING
     if (key == "dbg") { dbg_ = (int)value; dev_->B.dbg = dbg_; drop_graph(); return; }
 #endif
-    if (key == "host_results") { host_results_ = value != 0; reduced_downloaded_ = false; }
-    else if (key == "shape_descriptors") shape_descriptors_ = value != 0;      // (robots added FROM NOW ON carry the surface mesh)
-    else if (key == "steps_per_launch") steps_per_launch_ = (int)value;
-    else if (key == "graph_steps") { graph_steps_ = (int)value; drop_graph(); }
-    else {
-        const double now = key == "wide" ? (double)wide_ : key == "wide_two_tiles" ? (double)wide_two_tiles_ : key == "col_cap" ? (double)col_cap_ :
-                           key == "tiled" ? (double)tiled_ : key == "tile_small" ? (double)tile_small_ : key == "fused" ? (double)fused_ :
-                           key == "pair" ? (double)pair_ : key == "pair_sel" ? (double)pair_sel_ : (double)tiles_per_robot_;
-        const double want = (key == "wide" || key == "wide_two_tiles" || key == "tile_small" || key == "fused" || key == "pair_sel") ? (double)(value != 0) : (double)(int)value;
-        if (now == want) return;              // (unchanged: the assembled batch stays)
+    const OptionDesc& d = find_option(key);
+    const int want = d.coerce(value);
+    if (d.batch) {
+        if (opt_.*d.member == want) return;   // (unchanged: the assembled batch stays)
         prepared_ = false;                    // (the batch is assembled again at the next run)
-        if (key == "fused") { fused_ = value != 0; drop_graph(); }
-        else if (key == "pair") pair_ = (int)value;
-        else if (key == "pair_sel") pair_sel_ = value != 0;
-        else if (key == "wide") wide_ = value != 0;
-        else if (key == "wide_two_tiles") wide_two_tiles_ = value != 0;
-        else if (key == "col_cap") col_cap_ = (int)value;
-        else if (key == "tiled") tiled_ = (int)value;
-        else if (key == "tile_small") tile_small_ = value != 0;
-        else tiles_per_robot_ = (int)value;
     }
+    opt_.*d.member = want;
+    if (d.graph) drop_graph();
+    if (d.member == &Options::host_results) reduced_downloaded_ = false;
 }
 
 // where the host-side time of a run goes (VXH_PROF_HOST=1: one line per prepare() / advance() on stderr)
@@ -604,6 +607,91 @@ struct HostStages {
 };
 }
 
+// Which kernel steps which robot: functions of the robot alone (and of the engine's options), never of the batch.
+namespace {
+// Wide kernel (kernels_wide.hpp; robots of up to WIDE_BLOCK voxels and 1023 bonds): its bond records share their LDS region with
+// the scratch of the whole-robot passes (12 * BLOCK doubles, then the mesh vertices of a robot in a fluid); the record that stays
+// zero lies behind both.
+constexpr int WIDE_BLOCK = 512;
+struct WideLayout { int zidx = 0, region = 0; };
+WideLayout wide_layout(const RobotModel& M, int variant)
+{
+    WideLayout W;
+    const bool in_fluid = variant == 1 && M.vxa.fluid_env;
+    const int scratch = 12 * WIDE_BLOCK + (in_fluid ? 3 * ((M.nvox + 63) / 64 * 64) + 3 * M.nmv : 0);
+    W.zidx = std::max(M.nbond, (scratch + VXH_WIDE_REC - 1) / VXH_WIDE_REC);
+    W.region = (VXH_WIDE_REC * (W.zidx + 1) + 1) & ~1;
+    return W;
+}
+bool wide_listed(const RobotModel& M, int variant, const Options& opt)
+{
+    return opt.wide && M.nvox > 0 && M.nvox <= WIDE_BLOCK && M.nbond <= 1023 && M.bond_classes.size() <= 4095 && wide_layout(M, variant).zidx <= 1023;
+}
+// workgroup size of the resident kernel for a robot of n voxels: its size class
+int resident_block(int n) { return n <= 256 ? 256 : (n <= 512 ? 512 : (n <= 768 ? 768 : 1024)); }
+
+// Resident kernel (kernels_fused.hpp) or wide kernel, one workgroup per robot: the variant follows from the robot's size, fluid, and the
+// LDS need of its own tables.  block == 0: neither takes the robot.
+struct FusedVariant { int block = 0, nacc = 0, fluid = 0, tabg = 0, wide = 0, two_tiles = 0; size_t lds = 0; };
+FusedVariant fused_variant(const RobotModel& M, int variant, const Options& opt)
+{
+    FusedVariant fv;
+    const size_t lds_max = 160 * 1024 - VXH_FUSED_STATIC_LDS;
+    const int n = M.nvox;
+    if (n == 0 || n > 1024 || M.bond_classes.size() > 4095) return fv;   // (12 class bits in a bond entry; a robot of 1024 voxels has at most 3072 bonds)
+    if (wide_listed(M, variant, opt)) {
+        // the wide kernel when its LDS layout fits (mirrors the top of k_robot_wide): pose tile, record region, class tables,
+        // the strain tile of a land_water robot, the mask + pool of the contact rows
+        const WideLayout W = wide_layout(M, variant);
+        const int mesh = M.nmv > 0 ? 1 : 0;
+        auto wneed = [&](bool tables_in_lds) {
+            return (size_t)(8 * WIDE_BLOCK + W.region) * 8 +
+                   (tables_in_lds ? M.bond_classes.size() * sizeof(DBondClass) + M.vox_classes.size() * sizeof(DVoxClass) : 0) +
+                   (mesh ? (size_t)48 * WIDE_BLOCK : 0) + (M.vxa.self_col_enabled ? (size_t)8 * WIDE_BLOCK : 0);
+        };
+        const int wtabg = wneed(true) > lds_max ? 1 : 0;
+        if (wneed(!wtabg) <= lds_max) {
+            fv.block = WIDE_BLOCK; fv.nacc = 0; fv.fluid = mesh; fv.tabg = wtabg; fv.wide = 1; fv.lds = wneed(!wtabg);
+            // a second pose tile (64 B per thread) where the layout leaves room for it and, for a colliding robot, for at least
+            // 8 KB of contact rows: the step then has two workgroup barriers instead of three (kernels_wide.hpp)
+            const size_t tile = (size_t)64 * WIDE_BLOCK, rows_min = M.vxa.self_col_enabled ? (size_t)8 * 1024 : 0;
+            if (opt.wide_two_tiles && fv.lds + tile + rows_min <= lds_max) fv.two_tiles = 1;
+            const size_t room = lds_max - (fv.two_tiles ? tile : 0);
+            if (M.vxa.self_col_enabled && room > fv.lds) fv.lds += std::min<size_t>(room - fv.lds, (size_t)24 * 1024);
+            fv.lds &= ~(size_t)7;
+            if (fv.two_tiles) fv.lds += tile;
+            return fv;
+        }
+    }
+    const int block = resident_block(n);
+    const int fluid = M.nmv > 0 ? 1 : 0;      // (the MESH variants: every land_water robot carries the surface mesh)
+    const bool in_fluid = variant == 1 && M.vxa.fluid_env;
+    // LDS need: pose tile, accumulator tiles, actuation phases; class tables; the mesh vertices of a robot in a
+    // fluid; with two accumulator tiles the MESH variants also hold the strain tile (with one it stays in HBM)
+    // (mirrors the layout at the top of k_robot_steps; SLIM = the 768-thread MESH variant, phases and strains in HBM)
+    const bool slim = fluid && block == 768;
+    auto need = [&](int nacc, bool tables_in_lds) {
+        return (size_t)(8 + 6 * nacc + (slim ? 0 : 2)) * block * 8 +
+               (tables_in_lds ? M.bond_classes.size() * sizeof(DBondClass) + M.vox_classes.size() * sizeof(DVoxClass) : 0) +
+               (in_fluid ? (size_t)24 * M.nmv : 0) + ((fluid && nacc == 2 && !slim) ? (size_t)48 * block : 0);
+    };
+    // accumulator tiles: two up to 768 voxels, one for 1024; class tables in LDS unless they do not fit (per-voxel
+    // evolved stiffness makes nearly every bond a class of its own), then the TABG variant reads them from HBM
+    const int nacc = block == 1024 ? 1 : 2;
+    const int tabg = need(nacc, true) > lds_max ? 1 : 0;
+    if (need(nacc, !tabg) > lds_max) return fv;                   // (e.g. a mesh with thousands of vertices)
+    fv.block = block; fv.nacc = nacc; fv.fluid = fluid; fv.tabg = tabg; fv.lds = need(nacc, !tabg);
+    // colliding robots: what the workgroup can spare without lowering the number of workgroups a CU holds (two of the 256-thread
+    // variant, by its registers; one of the others) takes the contact rows, 12 bytes per listed pair
+    if (M.vxa.self_col_enabled) {
+        const size_t room = (block == 256 ? (size_t)80 * 1024 - VXH_FUSED_STATIC_LDS : lds_max);
+        if (room > fv.lds) fv.lds += std::min<size_t>(room - fv.lds, (size_t)24 * 1024);
+    }
+    fv.lds &= ~(size_t)7;
+    return fv;
+}
+}  // namespace
+
 void Engine::prepare()
 {
     HostStages hs;
@@ -612,22 +700,6 @@ void Engine::prepare()
     D.free_all();
     hs.mark("free");
     const int nr = (int)robots_.size();
-    // Wide kernel (kernels_wide.hpp; robots of up to WIDE_BLOCK voxels and 1023 bonds): its bond records share their LDS region with
-    // the scratch of the whole-robot passes (12 * BLOCK doubles, then the mesh vertices of a robot in a fluid); the record that stays
-    // zero lies behind both.  A function of the robot alone, like every kernel choice.
-    constexpr int WIDE_BLOCK = 512;
-    struct WideLayout { int zidx = 0, region = 0; };
-    auto wide_layout = [&](const RobotModel& M) {
-        WideLayout W;
-        const bool in_fluid = variant_ == 1 && M.vxa.fluid_env;
-        const int scratch = 12 * WIDE_BLOCK + (in_fluid ? 3 * ((M.nvox + 63) / 64 * 64) + 3 * M.nmv : 0);
-        W.zidx = std::max(M.nbond, (scratch + VXH_WIDE_REC - 1) / VXH_WIDE_REC);
-        W.region = (VXH_WIDE_REC * (W.zidx + 1) + 1) & ~1;
-        return W;
-    };
-    auto wide_listed = [&](const RobotModel& M) {
-        return wide_ && M.nvox > 0 && M.nvox <= WIDE_BLOCK && M.nbond <= 1023 && M.bond_classes.size() <= 4095 && wide_layout(M).zidx <= 1023;
-    };
     std::vector<DVoxClass> vtab;
     std::vector<DBondClass> btab;
     D.h_robot.assign(nr, DRobot{});
@@ -669,15 +741,9 @@ void Engine::prepare()
     std::vector<unsigned short> vclass(nv, 0);
     std::vector<short> bclass((size_t)3 * nv, -1);
     // bond schedules of the resident kernel: [3][block] per robot, block = the workgroup size of the robot's size class
-    auto resident_block = [](int n) { return n <= 256 ? 256 : (n <= 512 ? 512 : (n <= 768 ? 768 : 1024)); };
-    // Pair kernel (kernels_pair.hpp): 512 threads, two voxels and up to two bonds per axis per lane -- the large robots without a surface
-    // mesh that the wide kernel does not take.  A function of the robot alone (and of the engine's options), like every kernel choice.
-    auto uses_pair = [&](const RobotModel& M) {
-        return pair_ > 0 && M.nmv == 0 && M.nvox > (pair_ == 2 ? 512 : 768) && M.nvox <= 1024 && M.bond_classes.size() <= 4095 && !wide_listed(M);
-    };
     std::vector<int> sched_off(nr + 1, 0);
     for (int r = 0; r < nr; ++r)
-        sched_off[r + 1] = sched_off[r] + ((robots_[r].nvox > 0 && robots_[r].nvox <= 1024) ? (uses_pair(robots_[r]) ? 6 * VXH_PAIR_T : 3 * resident_block(robots_[r].nvox)) : 0);
+        sched_off[r + 1] = sched_off[r] + ((robots_[r].nvox > 0 && robots_[r].nvox <= 1024) ? 3 * resident_block(robots_[r].nvox) : 0);
     std::vector<int> bsched(std::max(sched_off[nr], 1), -1);
     std::vector<int> wgather((size_t)2 * nv, 0);
     std::vector<float> amp_damp(nv, 1.f);
@@ -720,7 +786,7 @@ void Engine::prepare()
     // below 64, and the engine says so -- a row that then overflows gives its robot VXH_ROBOT_COL_OVERFLOW, as with a col_cap of the
     // user's.  (Round 3 allocated nsurf^2 whatever the size and ran out of memory in this function for lattices it used to step.)
     long long row_limit = 0x7fffffff;
-    if (col_cap_ <= 0) {
+    if (opt_.col_cap <= 0) {
         double want = 0, rows = 0;
         for (int r = 0; r < nr; ++r) if (robots_[r].vxa.self_col_enabled) { want += 16.0 * (double)robots_[r].nsurf * (double)std::max(1, robots_[r].nsurf - 1); rows += robots_[r].nsurf; }
         // (the budget is a third of the device's TOTAL memory, not of what happens to be free: how long a row can grow -- and with it whether a
@@ -739,9 +805,9 @@ void Engine::prepare()
         vtab_off[r + 1] = vtab_off[r] + (int)M.vox_classes.size();
         btab_off[r + 1] = btab_off[r] + (int)M.bond_classes.size();
         excl_off[r + 1] = excl_off[r] + (M.vxa.self_col_enabled ? (long long)M.nsurf * ((M.nsurf + 63) / 64) : 0);
-        col_cap[r] = M.vxa.self_col_enabled ? std::max(1, col_cap_ > 0 ? std::min(col_cap_, M.nsurf - 1) : (int)std::min<long long>(row_limit, M.nsurf - 1)) : 0;
+        col_cap[r] = M.vxa.self_col_enabled ? std::max(1, opt_.col_cap > 0 ? std::min(opt_.col_cap, M.nsurf - 1) : (int)std::min<long long>(row_limit, M.nsurf - 1)) : 0;
         col_off[r + 1] = col_off[r] + (long long)col_cap[r] * (M.vxa.self_col_enabled ? M.nsurf : 0);
-        wl_off[r + 1] = wl_off[r] + (wide_listed(M) ? M.nbond : 0);
+        wl_off[r + 1] = wl_off[r] + (wide_listed(M, variant_, opt_) ? M.nbond : 0);
     }
     std::vector<int> wlist(std::max(wl_off[nr], 1), -1);
     col_total = col_off[nr];
@@ -813,28 +879,6 @@ void Engine::prepare()
                     const int c = M.bond_class[(size_t)v * 3 + a];
                     if (c >= 0) list[a].push_back((int)((unsigned)v | ((unsigned)M.nbr[(size_t)v * 6 + 2 * a] << 10) | ((unsigned)c << 20)));
                 }
-            if (uses_pair(M)) {
-                // k_robot_pair: [3 axes][2 slots][512 threads].  X and Y are evaluated in ONE barrier-free stretch (four slots per lane), Z
-                // in a second one (two): the 64-bond chunks of X, then of Y, go round the eight wavefronts (wavefront w runs on SIMD w mod 4),
-                // so the four SIMDs carry the same number of chunk executions to within one; Z likewise on its own.
-                int* const sch = &bsched[sched_off[r]];
-                int used_xy[VXH_PAIR_NW][2] = {}, next_wave = 0;      // slots taken per wavefront: [X, Y]
-                for (int a = 0; a < 2; ++a) {
-                    const int nch = ((int)list[a].size() + 63) / 64;
-                    for (int c = 0; c < nch; ++c) {
-                        int w = next_wave;
-                        while (used_xy[w][a] >= 2) w = (w + 1) % VXH_PAIR_NW;          // (at most 16 chunks per axis: a free slot exists)
-                        next_wave = (w + 1) % VXH_PAIR_NW;
-                        int* dst = sch + (2 * a + used_xy[w][a]++) * VXH_PAIR_T + 64 * w;
-                        for (int k = 0; k < 64 && (size_t)(64 * c + k) < list[a].size(); ++k) dst[k] = list[a][(size_t)64 * c + k];
-                    }
-                }
-                const int nchz = ((int)list[2].size() + 63) / 64;
-                for (int c = 0; c < nchz; ++c) {
-                    int* dst = sch + (4 + c / VXH_PAIR_NW) * VXH_PAIR_T + 64 * (c % VXH_PAIR_NW);
-                    for (int k = 0; k < 64 && (size_t)(64 * c + k) < list[2].size(); ++k) dst[k] = list[2][(size_t)64 * c + k];
-                }
-            } else {
             for (size_t j = 0; j < list[0].size(); ++j) sx[j] = list[0][j];
             for (size_t j = 0; j < list[2].size(); ++j) sz[j] = list[2][j];
             if (block == 1024) { for (size_t j = 0; j < list[1].size(); ++j) sy[j] = list[1][j]; }
@@ -853,13 +897,12 @@ void Engine::prepare()
                     for (int k = 0; k < 64 && (size_t)(64 * c + k) < list[1].size(); ++k) sy[64 * best + k] = list[1][(size_t)64 * c + k];
                 }
             }
-            }
         }
         R.wl_begin = wl_off[r]; R.wnbond = 0; R.wzidx = 0; R.wregion = 0;
-        if (wide_listed(M)) {
+        if (wide_listed(M, variant_, opt_)) {
             // wide kernel: all bonds in one list, axis after axis; a bond's place in it is the number of its record, and every voxel
             // learns the records of its six directions (+A: the bond it is the negative end of; -A: that of its -A neighbour)
-            const WideLayout W = wide_layout(M);
+            const WideLayout W = wide_layout(M, variant_);
             std::vector<int> slot_of((size_t)M.nvox * 3, -1);
             int t = 0;
             for (int a = 0; a < 3; ++a)
@@ -1046,77 +1089,6 @@ void Engine::prepare()
     B.col_partner = D.alloc_raw<int>((size_t)std::max<long long>(col_off[nr], 1));     // (entries beyond col_cnt are never read)
     B.col_a1 = D.alloc_raw<double>((size_t)std::max<long long>(col_off[nr], 1));
     hs.mark("allocations + uploads");
-    // Which kernel steps which robot.  Resident kernel (kernels_fused.hpp), one workgroup per robot: its variant is a function
-    // of the robot alone (size, fluid, LDS need of its own tables), never of the batch.
-    struct FusedVariant { int block = 0, nacc = 0, fluid = 0, tabg = 0, wide = 0, two_tiles = 0, pair = 0; size_t lds = 0; };
-    auto fused_variant = [&](const RobotModel& M) {
-        FusedVariant fv;
-        const size_t lds_max = 160 * 1024 - VXH_FUSED_STATIC_LDS;
-        const int n = M.nvox;
-        if (n == 0 || n > 1024 || M.bond_classes.size() > 4095) return fv;   // (12 class bits in a bond entry; a robot of 1024 voxels has at most 3072 bonds)
-        if (wide_listed(M)) {
-            // the wide kernel when its LDS layout fits (mirrors the top of k_robot_wide): pose tile, record region, class tables,
-            // the strain tile of a land_water robot, the mask + pool of the contact rows
-            const WideLayout W = wide_layout(M);
-            const int mesh = M.nmv > 0 ? 1 : 0;
-            auto wneed = [&](bool tables_in_lds) {
-                return (size_t)(8 * WIDE_BLOCK + W.region) * 8 +
-                       (tables_in_lds ? M.bond_classes.size() * sizeof(DBondClass) + M.vox_classes.size() * sizeof(DVoxClass) : 0) +
-                       (mesh ? (size_t)48 * WIDE_BLOCK : 0) + (M.vxa.self_col_enabled ? (size_t)8 * WIDE_BLOCK : 0);
-            };
-            const int wtabg = wneed(true) > lds_max ? 1 : 0;
-            if (wneed(!wtabg) <= lds_max) {
-                fv.block = WIDE_BLOCK; fv.nacc = 0; fv.fluid = mesh; fv.tabg = wtabg; fv.wide = 1; fv.lds = wneed(!wtabg);
-                // a second pose tile (64 B per thread) where the layout leaves room for it and, for a colliding robot, for at least
-                // 8 KB of contact rows: the step then has two workgroup barriers instead of three (kernels_wide.hpp)
-                const size_t tile = (size_t)64 * WIDE_BLOCK, rows_min = M.vxa.self_col_enabled ? (size_t)8 * 1024 : 0;
-                if (wide_two_tiles_ && fv.lds + tile + rows_min <= lds_max) fv.two_tiles = 1;
-                const size_t room = lds_max - (fv.two_tiles ? tile : 0);
-                if (M.vxa.self_col_enabled && room > fv.lds) fv.lds += std::min<size_t>(room - fv.lds, (size_t)24 * 1024);
-                fv.lds &= ~(size_t)7;
-                if (fv.two_tiles) fv.lds += tile;
-                return fv;
-            }
-        }
-        if (uses_pair(M)) {
-            // pair kernel (mirrors the top of k_robot_pair): pose tile, class tables, one accumulator tile; a colliding robot gets what is
-            // left of the CU's LDS (one workgroup per CU anyway): the mask, the contact-row pool, and -- the whole stretch from the
-            // accumulators on -- the scratch of the broad-phase bit matrix
-            const size_t tabs = (M.bond_classes.size() * sizeof(DBondClass) + M.vox_classes.size() * sizeof(DVoxClass) + 15) & ~(size_t)15;
-            const size_t fixed = (size_t)(8 + 6) * VXH_PAIR_NV * 8;
-            const int ptabg = fixed + tabs + (M.vxa.self_col_enabled ? (size_t)(8 + 12) * 1024 : 0) > lds_max ? 1 : 0;
-            fv.block = VXH_PAIR_T; fv.nacc = 1; fv.fluid = 0; fv.tabg = ptabg; fv.pair = pair_sel_ ? 2 : 1;
-            fv.lds = M.vxa.self_col_enabled ? lds_max : fixed + (ptabg ? 0 : tabs);
-            fv.lds &= ~(size_t)7;
-            return fv;
-        }
-        const int block = n <= 256 ? 256 : (n <= 512 ? 512 : (n <= 768 ? 768 : 1024));
-        const int fluid = M.nmv > 0 ? 1 : 0;      // (the MESH variants: every land_water robot carries the surface mesh)
-        const bool in_fluid = variant_ == 1 && M.vxa.fluid_env;
-        // LDS need: pose tile, accumulator tiles, actuation phases; class tables; the mesh vertices of a robot in a
-        // fluid; with two accumulator tiles the MESH variants also hold the strain tile (with one it stays in HBM)
-        // (mirrors the layout at the top of k_robot_steps; SLIM = the 768-thread MESH variant, phases and strains in HBM)
-        const bool slim = fluid && block == 768;
-        auto need = [&](int nacc, bool tables_in_lds) {
-            return (size_t)(8 + 6 * nacc + (slim ? 0 : 2)) * block * 8 +
-                   (tables_in_lds ? M.bond_classes.size() * sizeof(DBondClass) + M.vox_classes.size() * sizeof(DVoxClass) : 0) +
-                   (in_fluid ? (size_t)24 * M.nmv : 0) + ((fluid && nacc == 2 && !slim) ? (size_t)48 * block : 0);
-        };
-        // accumulator tiles: two up to 768 voxels, one for 1024; class tables in LDS unless they do not fit (per-voxel
-        // evolved stiffness makes nearly every bond a class of its own), then the TABG variant reads them from HBM
-        const int nacc = block == 1024 ? 1 : 2;
-        const int tabg = need(nacc, true) > lds_max ? 1 : 0;
-        if (need(nacc, !tabg) > lds_max) return fv;                   // (e.g. a mesh with thousands of vertices)
-        fv.block = block; fv.nacc = nacc; fv.fluid = fluid; fv.tabg = tabg; fv.lds = need(nacc, !tabg);
-        // colliding robots: what the workgroup can spare without lowering the number of workgroups a CU holds (two of the 256-thread
-        // variant, by its registers; one of the others) takes the contact rows, 12 bytes per listed pair
-        if (M.vxa.self_col_enabled) {
-            const size_t room = (block == 256 ? (size_t)80 * 1024 - VXH_FUSED_STATIC_LDS : lds_max);
-            if (room > fv.lds) fv.lds += std::min<size_t>(room - fv.lds, (size_t)24 * 1024);
-        }
-        fv.lds &= ~(size_t)7;
-        return fv;
-    };
     // Tiled kernel (kernels_tiled.hpp), several workgroups per robot: for robots the resident kernel cannot take, and for
     // populations too small to give every CU a robot.  The number of tiles depends on the population (the results do not:
     // the tiled kernel's arithmetic per bond and per voxel, and its summation orders, are those of the resident kernel).
@@ -1130,7 +1102,7 @@ void Engine::prepare()
     std::vector<unsigned char> tile_fcount;
     bool any_fluid_tiles = false;
     int nx_total = 0;
-    const int tiled_now = tiling_allowed_ ? tiled_ : 0;
+    const int tiled_now = tiling_allowed_ ? opt_.tiled : 0;
     if (tiled_now > 0) {
         const size_t lds_cap = 160 * 1024 - VXH_TILE_STATIC_LDS;
         int n_work = 0;
@@ -1145,7 +1117,7 @@ void Engine::prepare()
         // launch) -- i.e. large robots (the 768- and 1024-thread variants) in populations of at most a quarter of the CUs.  (Until late in
         // round 2 the default was "any robot, up to three quarters of the CUs": slower for every size below 10^3, 2x slower at 128 robots,
         // and population-dependent in the last bits.)
-        const bool small_population = tile_small_ && n_work * 4 <= D.n_cu;
+        const bool small_population = opt_.tile_small && n_work * 4 <= D.n_cu;
         std::vector<int> cand;
         for (int r = 0; r < nr; ++r) {
             const RobotModel& M = robots_[r];
@@ -1153,8 +1125,8 @@ void Engine::prepare()
             // round 5, in a FLUID: the tile then carries its part of the drag mesh, and the voxels a mesh vertex averages over -- up to
             // seven, across tile boundaries, diagonal neighbours included -- come through the exchange buffer with their strains
             if (M.nvox == 0) continue;
-            const int block = fused_variant(M).block;
-            if (tiled_now == 2 || !fused_ || block == 0 || (small_population && block >= 768)) cand.push_back(r);
+            const int block = fused_variant(M, variant_, opt_).block;
+            if (tiled_now == 2 || !opt_.fused || block == 0 || (small_population && block >= 768)) cand.push_back(r);
         }
         // tiles per robot: one bond per lane and one WAVEFRONT of owned voxels per tile if the CUs allow it (a step then costs one bond
         // evaluation + one voxel update on one wavefront + the barrier), fewer when the candidates outnumber the CUs.  (Until late in
@@ -1193,7 +1165,7 @@ void Engine::prepare()
             const RobotModel& M = robots_[r];
             const int tab_doubles = (int)(M.bond_classes.size() * sizeof(DBondClass) / 8 + M.vox_classes.size() * sizeof(DVoxClass) / 8);
             const int tabg = (size_t)tab_doubles * 8 > 32 * 1024 ? 1 : 0;
-            int k = tiles_per_robot_ > 0 ? tiles_per_robot_
+            int k = opt_.tiles_per_robot > 0 ? opt_.tiles_per_robot
                                          : (sum_lat <= D.n_cu ? k_latency(M) : std::max(1, (int)(k_latency(M) * (long long)D.n_cu / sum_lat)));
             k = std::max(1, std::min(k, M.nvox / 8));
             for (;;) {
@@ -1215,19 +1187,18 @@ void Engine::prepare()
             }
         }
         // launches: all tiles of a robot in one launch, a launch no larger than what the chip keeps resident (the tiles of a
-        // robot wait for each other).  How many workgroups of THIS kernel a CU holds is asked of the runtime (registers, wavefront
-        // slots and LDS of the compiled code: five wavefronts of 256 vector registers are one workgroup per CU, whatever the LDS says)
+        // robot wait for each other): ONE workgroup per CU -- four wavefronts of up to 512 registers each fill the register files of a CU
+        // whatever the LDS says, and an over-estimate ends in VXH_ROBOT_SYNC_TIMEOUT replays, an under-estimate only in smaller launches
+        const long long capacity = D.n_cu;
         for (int kind = 0; kind < 12; ++kind) {
             const int tabg = kind & 1, mesh = (kind >> 1) % 3, small = kind / 6;      // mesh: 0 _voxcad, 1 land_water on land, 2 land_water in a fluid
             Device::TileLaunch cur;
             cur.tabg = tabg; cur.mesh = mesh; cur.small = small;
-            auto capacity = [&](size_t lds) { return (long long)D.n_cu * tile_workgroups_per_cu(tabg, mesh, lds); };
             for (auto& q : planned) {
                 if (q.tabg != tabg || q.mesh != mesh || q.small != small) continue;
                 const int k = q.plan.k;
-                if (k > capacity(q.lds)) continue;                    // more tiles than the chip holds: not tiled
-                const size_t lds = std::max(cur.lds, q.lds);
-                if (cur.count > 0 && cur.count + k > capacity(lds)) { D.tile_launches.push_back(cur); cur = Device::TileLaunch(); cur.tabg = tabg; cur.mesh = mesh; cur.small = small; }
+                if (k > capacity) continue;                    // more tiles than the chip holds: not tiled
+                if (cur.count > 0 && cur.count + k > capacity) { D.tile_launches.push_back(cur); cur = Device::TileLaunch(); cur.tabg = tabg; cur.mesh = mesh; cur.small = small; }
                 cur.lds = std::max(cur.lds, q.lds);
                 const int tile0 = (int)h_tiles.size(), base = D.vox_begin[q.r];
                 for (int t = 0; t < k; ++t) {
@@ -1309,8 +1280,8 @@ void Engine::prepare()
             // speed, and the whole robot waits for them at every barrier; asking for more than half of the LDS keeps them apart.
             if (L.count <= D.n_cu) L.lds = std::max(L.lds, (size_t)(81 * 1024));
             if (std::getenv("VXH_PROF_TILES"))
-                std::fprintf(stderr, "vxhip: tile launch kind tabg=%d mesh=%d: %d tiles of %zu robots, %zu B of LDS, %lld workgroups per CU\n", L.tabg, L.mesh, L.count,
-                             L.robots.size(), L.lds, tile_workgroups_per_cu(L.tabg, L.mesh, L.lds));
+                std::fprintf(stderr, "vxhip: tile launch kind tabg=%d mesh=%d: %d tiles of %zu robots, %zu B of LDS, 1 workgroups per CU\n", L.tabg, L.mesh, L.count,
+                             L.robots.size(), L.lds);
         }
     }
     {
@@ -1352,11 +1323,11 @@ void Engine::prepare()
         D.groups.clear();
         for (int r = 0; r < nr; ++r) {
             if (D.robot_tiled[r]) continue;
-            const FusedVariant fv = fused_variant(robots_[r]);
+            const FusedVariant fv = fused_variant(robots_[r], variant_, opt_);
             if (fv.block == 0) continue;                              // streaming kernels
             Device::Group* g = nullptr;
-            for (auto& q : D.groups) if (q.block == fv.block && q.nacc == fv.nacc && q.fluid == fv.fluid && q.tabg == fv.tabg && q.wide == fv.wide && q.two_tiles == fv.two_tiles && q.pair == fv.pair) g = &q;
-            if (!g) { D.groups.emplace_back(); g = &D.groups.back(); g->block = fv.block; g->nacc = fv.nacc; g->fluid = fv.fluid; g->tabg = fv.tabg; g->wide = fv.wide; g->two_tiles = fv.two_tiles; g->pair = fv.pair; }
+            for (auto& q : D.groups) if (q.block == fv.block && q.nacc == fv.nacc && q.fluid == fv.fluid && q.tabg == fv.tabg && q.wide == fv.wide && q.two_tiles == fv.two_tiles) g = &q;
+            if (!g) { D.groups.emplace_back(); g = &D.groups.back(); g->block = fv.block; g->nacc = fv.nacc; g->fluid = fv.fluid; g->tabg = fv.tabg; g->wide = fv.wide; g->two_tiles = fv.two_tiles; }
             g->robots.push_back(r);
             g->lds = std::max(g->lds, fv.lds);
         }
@@ -1378,7 +1349,7 @@ void Engine::prepare()
             g.count = (int)g.robots.size();
             g.list = D.upload(g.robots);
             g.order_valid = false; g.order_cur = 0; g.order_use = false;
-            if (!g.wide && !g.pair) {       // (k_robot_steps; colliding robots only: the others have no broad-phase runs to spread)
+            if (!g.wide) {                  // (k_robot_steps; colliding robots only: the others have no broad-phase runs to spread)
                 for (int r : g.robots) if (robots_[r].vxa.self_col_enabled) g.order_use = true;
                 if (g.order_use) for (int k = 0; k < 2; ++k) g.order_bits[k] = D.alloc_zero<unsigned long long>((size_t)(g.count + 63) / 64 + 1);
             }
@@ -1429,14 +1400,9 @@ void Engine::prepare()
 
 void Engine::reset() { if (!robots_.empty()) prepare(); }
 
-static void launch_group(const DBatch& B, int block, bool fluid, bool tabg, bool wide, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters, int two_tiles = 0, int pair = 0,
+static void launch_group(const DBatch& B, int block, bool fluid, bool tabg, bool wide, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters, int two_tiles = 0,
                          const unsigned long long* order_in = nullptr, unsigned long long* order_out = nullptr)
 {
-#ifdef VXH_PAIR
-    if (pair) { launch_pair_group(B, tabg, pair == 2, list, count, lds, s, cap, iters); return; }
-#else
-    (void)pair;                               // (check_option refuses `pair` in a library built without -DVXH_PAIR)
-#endif
     if (wide) { launch_wide_group(B, fluid, tabg, list, count, lds, s, cap, iters, two_tiles); return; }
     if (fluid) launch_fused_mesh(B, block, tabg, list, count, lds, s, cap, iters, order_in, order_out);
     else launch_fused_land(B, block, tabg, list, count, lds, s, cap, iters, order_in, order_out);
@@ -1459,11 +1425,11 @@ void Engine::advance(long long max_rounds)
         // from the start up to where this call was to end -- a call in the middle of a run too (round 4; until then only a call that
         // started from the imported state was made again, and with several `voxelyze` processes on one GPU, the reference's own
         // launch pattern, this is the path that is hit).  The tiled kernel stays off for this engine.
-        if (tiled_ == 0 || !tiling_allowed_) throw;
+        if (opt_.tiled == 0 || !tiling_allowed_) throw;
         std::fprintf(stderr, "vxhip: %s -- this batch is stepped again%s without the tiled kernel, which stays off for this engine\n", e.what(),
                      before != 0 ? " from its imported state" : "");
         dev_->pending.active = false;
-        tiled_ = 0;
+        opt_.tiled = 0;
         prepare();
         const long long huge = 0x7fffffffffffffffLL / 4;
         advance_launch(max_rounds >= huge - before ? huge : before + max_rounds);
@@ -1498,7 +1464,7 @@ void Engine::advance_launch(long long max_rounds)
     const long long cap = (max_rounds >= remaining) ? cap_all : rounds_done_ + max_rounds;
     // robots that fit the resident kernel are stepped by their launch groups, the others (more than 1024 voxels, oversized
     // mesh) by the streaming kernels, side by side on their own streams; with the option fused = 0 everything streams
-    const bool fused = fused_ && !D.groups.empty();
+    const bool fused = opt_.fused && !D.groups.empty();
     const bool tiled = !D.tile_launches.empty();
     const bool streaming = fused ? D.n_rest > 0 : D.n_all > 0;
     B.streamed = fused ? D.streamed_rest : D.streamed_all;
@@ -1522,7 +1488,7 @@ void Engine::advance_launch(long long max_rounds)
     // longer in every variant tried -- list re-sorted and copied, partitioned and copied from pinned memory, read by the kernel from
     // mapped host memory -- which is more than the launch gained.  Polling the last event instead of sleeping on the stream: no gain.)
     if (fused) {
-        const int iters = std::max(1, steps_per_launch_);
+        const int iters = std::max(1, opt_.steps_per_launch);
         for (auto& g : D.groups) {
             if (single) break;               // (its span is the call's: ev0 .. ev1; every event record is a packet the command processor works through)
             HIP_OK(hipStreamWaitEvent(g.stream, D.ev0, 0));
@@ -1534,7 +1500,7 @@ void Engine::advance_launch(long long max_rounds)
                 // a short launch (what is left of the call, or the launch length itself): flagged robots first, flags for the next one
                 const long long len = std::min<long long>(iters, std::max<long long>(1, todo - done));
                 const bool dyn = g.order_use && g.order_valid && len <= VXH_ORDER_MAX_STEPS;
-                launch_group(B, g.block, g.fluid != 0, g.tabg != 0, g.wide != 0, g.list, g.count, g.lds, single ? D.stream : g.stream, cap, iters, g.two_tiles, g.pair,
+                launch_group(B, g.block, g.fluid != 0, g.tabg != 0, g.wide != 0, g.list, g.count, g.lds, single ? D.stream : g.stream, cap, iters, g.two_tiles,
                              dyn ? g.order_bits[g.order_cur] : nullptr, g.order_use ? g.order_bits[g.order_cur ^ 1] : nullptr);
                 if (g.order_use) { g.order_cur ^= 1; g.order_valid = true; }      // (every launch leaves the flags for the next)
                 ++launches; ++group_launches[k];
@@ -1546,10 +1512,10 @@ void Engine::advance_launch(long long max_rounds)
     if (tiled) {
         // every tiled launch on the one tile stream: the tiles of a robot wait for each other, so two such launches must never
         // compete for the CUs
-        // ... nor with anything else: the launches are sized for an empty chip (capacity() in prepare()), and the tiles of a robot that
+        // ... nor with anything else: the launches are sized for an empty chip (`capacity` in prepare()), and the tiles of a robot that
         // are already placed spin -- holding their CUs -- until the missing ones arrive.  In a mixed batch the tiled launches therefore
         // run AFTER the launch groups of the resident robots, and the streaming kernels after them.
-        const int iters = std::max(1, steps_per_launch_);
+        const int iters = std::max(1, opt_.steps_per_launch);
         HIP_OK(hipStreamWaitEvent(D.tile_stream, D.ev0, 0));
         if (fused) for (auto& g : D.groups) HIP_OK(hipStreamWaitEvent(D.tile_stream, g.t1, 0));
         HIP_OK(hipEventRecord(D.tile_t0, D.tile_stream));
@@ -1574,18 +1540,18 @@ void Engine::advance_launch(long long max_rounds)
             hipLaunchKernelGGL(k_voxels, dim3(nb_v), dim3(256), 0, D.stream, B);
         };
         long long launched = 0;
-        if (graph_steps_ > 1 && cap == cap_all && todo >= graph_steps_) {
-            if (!D.graph_exec || D.graph_rounds != graph_steps_ || D.graph_mask != B.streamed) {
+        if (opt_.graph_steps > 1 && cap == cap_all && todo >= opt_.graph_steps) {
+            if (!D.graph_exec || D.graph_rounds != opt_.graph_steps || D.graph_mask != B.streamed) {
                 if (D.graph_exec) { hipGraphExecDestroy(D.graph_exec); D.graph_exec = nullptr; }
                 if (D.graph) { hipGraphDestroy(D.graph); D.graph = nullptr; }
                 HIP_OK(hipStreamBeginCapture(D.stream, hipStreamCaptureModeThreadLocal));
-                for (int k = 0; k < graph_steps_; ++k) round(cap_all);
+                for (int k = 0; k < opt_.graph_steps; ++k) round(cap_all);
                 HIP_OK(hipStreamEndCapture(D.stream, &D.graph));
                 HIP_OK(hipGraphInstantiate(&D.graph_exec, D.graph, nullptr, nullptr, 0));
-                D.graph_rounds = graph_steps_;
+                D.graph_rounds = opt_.graph_steps;
                 D.graph_mask = B.streamed;
             }
-            while (todo - launched >= graph_steps_) { HIP_OK(hipGraphLaunch(D.graph_exec, D.stream)); launched += graph_steps_; }
+            while (todo - launched >= opt_.graph_steps) { HIP_OK(hipGraphLaunch(D.graph_exec, D.stream)); launched += opt_.graph_steps; }
         }
         for (; launched < todo; ++launched) round(cap);
         hipLaunchKernelGGL(k_step_begin, dim3(B.n_robots), dim3(256), 0, D.stream, B, cap, 0);   // finish the last step
@@ -1664,8 +1630,8 @@ void Engine::advance_finish()
         } else {
             float cms = 0;
             if (D.pending.single) cms = ms; else HIP_OK(hipEventElapsedTime(&cms, D.groups[best].t0, D.groups[best].t1));
-            // (the resident kernel's workgroup size; + 1: the wide kernel; 1026: the pair kernel -- 512 threads, 1024 voxel slots)
-            counters_.dominant_block = D.groups[best].pair ? VXH_PAIR_NV + 2 : D.groups[best].block + (D.groups[best].wide ? 1 : 0); counters_.dominant_robots = D.groups[best].count;
+            // (the resident kernel's workgroup size; + 1: the wide kernel)
+            counters_.dominant_block = D.groups[best].block + (D.groups[best].wide ? 1 : 0); counters_.dominant_robots = D.groups[best].count;
             counters_.dominant_launches = group_launches[best]; counters_.dominant_seconds = cms * 1e-3;
             counters_.dominant_alg_bytes = grp_ab[best]; counters_.dominant_voxel_steps = grp_vs[best];
         }
@@ -1872,7 +1838,7 @@ void Engine::result(int robot, vxh_result* out)
     if (!prepared_) throw std::logic_error("results requested before vxh_run/vxh_step");
     // _voxcad: every tag from the device-side reductions; land_water: the RobotVolume tags need the surface mesh of the final state
     // (poses + strains of every voxel), evaluated on the host
-    const bool need_state = variant_ == 1 || host_results_;
+    const bool need_state = variant_ == 1 || opt_.host_results;
     if (need_state && !state_downloaded_) download();
     if (!need_state && !reduced_downloaded_) download_reduced();
     HostState& H = host_[robot];

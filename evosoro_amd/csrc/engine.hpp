@@ -30,6 +30,27 @@ struct HostState {                      // final/current state of one robot, dow
 // imported state again without the tiled kernel; elsewhere it surfaces as VXH_ERR_HIP
 struct TileTimeout : std::runtime_error { using std::runtime_error::runtime_error; };
 
+// What vxh_set_option sets (include/vxhip.h documents the keys for the caller; the table in engine.hip describes each once: kind, accepted
+// values, whether it belongs to the assembled batch).  Flags are stored as 0 / 1.
+struct Options {
+    int tiled = 1;                             // several workgroups per robot (kernels_tiled.hpp): 0 never, 1 when the population is too
+                                               // small to fill the CUs one robot each or a robot has more than 1024 voxels, 2 always
+    int tiles_per_robot = 0;                   // 0 = chosen from the population size; > 0: requested for every tiled robot (tests)
+    int tile_small = 0;                        // also tile large robots the resident kernel could take when the population is small (see prepare())
+    int wide = 1;                              // small robots (up to 512 voxels, 1023 bonds) go to the wide kernel (kernels_wide.hpp); 0: resident kernel
+    int wide_two_tiles = 1;                    // ... with a second pose tile in LDS where it fits (two barriers per step instead of three); 0: cross-checks
+    int col_cap = 0;                           // partners a contact row can hold; 0 = every other surface voxel (unbounded, like the reference)
+    int fused = 1;                             // one-workgroup-per-robot fused kernel when every robot has <= 1024 voxels
+    // fused and tiled paths: time steps per kernel launch.  A launch of a self-colliding population carries ~0.07 ms of fixed cost (0.27 ms until round 3; it
+    // ends with its slowest workgroup: DESIGN.md "The cost of a launch"); a whole evaluation of the bench population (7806 steps),
+    // us per step by launch length: 256: 31.2 | 512: 30.7 | 1024: 30.6 | 2048: 30.6 | 8192 (one launch): 30.3.  (256 until late in round 2.)
+    int steps_per_launch = 1024;
+    int graph_steps = 32;                      // streaming path: step rounds captured per hipGraph launch (0 = plain launches)
+    int shape_descriptors = 0;                 // _voxcad robots added from now on carry the deformable surface mesh (voxelyze --computeShapeDescriptors): they are
+                                               // stepped by the MESH kernel variants, which record the directional strains the final mesh needs
+    int host_results = 0;                      // every result from the downloaded voxel state on the host (cross-check)
+};
+
 class Engine {
 public:
     Engine(int variant, int device_id);       // throws std::runtime_error when no HIP device is usable
@@ -89,32 +110,12 @@ private:
     std::vector<HostState> host_;
     std::unique_ptr<Device> dev_;
     bool prepared_ = false, state_downloaded_ = false, control_downloaded_ = false, reduced_downloaded_ = false;
-    bool host_results_ = false;                // option host_results: every result from the downloaded voxel state on the host (cross-check)
     long long rounds_done_ = 0;
-    int graph_steps_ = 32;                     // streaming path: step rounds captured per hipGraph launch (0 = plain launches)
-    int dbg_ = 0;
-    bool fused_ = true;                        // one-workgroup-per-robot fused kernel when every robot has <= 1024 voxels
-    // fused and tiled paths: time steps per kernel launch.  A launch of a self-colliding population carries ~0.07 ms of fixed cost (0.27 ms until round 3; it
-    // ends with its slowest workgroup: DESIGN.md "The cost of a launch"); a whole evaluation of the bench population (7806 steps),
-    // us per step by launch length: 256: 31.2 | 512: 30.7 | 1024: 30.6 | 2048: 30.6 | 8192 (one launch): 30.3.  (256 until late in round 2.)
-    int steps_per_launch_ = 1024;
+    Options opt_;
+    int dbg_ = 0;                              // developer library: physics-skipping what-if switches (option dbg)
     bool tiling_allowed_ = true;               // the handle's veto (set_tiling_allowed): several engines of one handle share this device
-    int tiled_ = 1;                            // several workgroups per robot (kernels_tiled.hpp): 0 never, 1 when the population is too
-                                               // small to fill the CUs one robot each or a robot has more than 1024 voxels, 2 always
-    int tiles_per_robot_ = 0;                  // 0 = chosen from the population size; > 0: requested for every tiled robot (tests)
     // fault injection for tests/test_gpu_tiled.py: VXH_INJECT_TILE_TIMEOUT=n, the n-th tiled call of the engine reports a timeout (1 = the first)
     int inject_tile_timeout_ = std::getenv("VXH_INJECT_TILE_TIMEOUT") ? std::max(1, std::atoi(std::getenv("VXH_INJECT_TILE_TIMEOUT"))) : 0;
-    bool wide_two_tiles_ = true;               // ... with a second pose tile in LDS where it fits (two barriers per step instead of three); 0: cross-checks
-    bool wide_ = true;                         // small robots (up to 512 voxels, 1023 bonds) go to the wide kernel (kernels_wide.hpp); 0: resident kernel
-    // k_robot_pair (kernels_pair.hpp: 512 threads, two voxels and up to two bonds per axis per lane) instead of k_robot_steps<1024> for robots of
-    // 769-1024 voxels without a surface mesh (1), also instead of <768> for those of 513-768 (2).  OFF by default: bit-identical to <1024>, but
-    // measured 20-30 % slower (round 5, DESIGN.md section 4 "Pair path": two wavefronts per SIMD do not hide the latency of a dependent FP64 chain)
-    int pair_ = 0;
-    bool shape_descriptors_ = false;           // _voxcad robots added from now on carry the deformable surface mesh (voxelyze --computeShapeDescriptors): they are
-                                               // stepped by the MESH kernel variants, which record the directional strains the final mesh needs
-    bool pair_sel_ = false;                    // ... with the rotation-vector factor in select form (kernels.hpp rotvec_factor<SEL>; A/B switch)
-    int col_cap_ = 0;                          // partners a contact row can hold; 0 = every other surface voxel (unbounded, like the reference)
-    bool tile_small_ = false;                  // also tile large robots the resident kernel could take when the population is small (see prepare())
     unsigned tile_gen_ = 0;                    // launch generation of the tiled kernel (high half of the tiles' flag words)
     vxh_counters counters_{};
 };

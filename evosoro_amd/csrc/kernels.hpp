@@ -310,7 +310,7 @@ __device__ __forceinline__ double one_minus_square(double w) { const double ww =
 //                   rounding of w w: on this branch sl > 2.4e-3, that rounding is a relative < 2.5e-14 of the result.
 //   else            acos(w) * rsqrt(sl) as before (never taken by a sane bond; kept for the function's contract).
 // The factor 2 of the rotation vector is folded into f (exact).
-// SEL (the resident kernel): the select form -- numerator and rsqrt argument of the lane's branch chosen first, ONE refined v_rsq_f64
+// SEL (the 768-thread resident kernel, kernels_fused.hpp fused_bond): the select form -- numerator and rsqrt argument of the lane's branch chosen first, ONE refined v_rsq_f64
 // for both (the same operations on the same values per lane as the branched form: same bits, scripts/dev_gpu_diag.py statehash).
 // Measured, same box: resident kernel 25.15 -> 24.96 us per step (its wavefronts are of both kinds, and run both branches); the wide
 // kernel the other way, 64 x 6^3 5.6 -> 5.7, swimmers 13.8 -> 14.0, 512 x 8^3 16.75 -> 17.05 -- hence a switch.
@@ -1230,8 +1230,5 @@ static __global__ __launch_bounds__(256) void k_voxels(DBatch B)
 }  // namespace vxh
 
 #include "kernels_fused.hpp"
-#ifdef VXH_PAIR      // measured 20-30 % slower than the kernels it replaces (DESIGN.md "Pair path"): kept for A/B in the developer library (make prof)
-#include "kernels_pair.hpp"
-#endif
 #include "kernels_wide.hpp"
 #include "kernels_tiled.hpp"

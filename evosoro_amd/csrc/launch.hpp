@@ -1,5 +1,5 @@
 // Host-side launch entry points of the stepping kernels.  Each kernel family is its own translation unit (launch_fused_*.hip,
-// launch_wide.hip, launch_tiled.hip, launch_pair.hip) so that the Makefile compiles them side by side and a change to one family
+// launch_wide.hip, launch_tiled.hip) so that the Makefile compiles them side by side and a change to one family
 // recompiles that family only; engine.hip (batch assembly, the call loop, the streaming kernels) sees these declarations.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -39,13 +39,7 @@ void launch_wide_group(const DBatch& B, bool mesh, bool tabg, const int* list, i
 // k_tile_steps<TABG, MESH, FLUID> (kernels_tiled.hpp); mesh_kind: 0 = _voxcad, 1 = land_water robot on land, 2 = in a fluid
 // small: every tile of the launch within VXH_TILE_S_OWN / _HALO / _BONDS (device_types.hpp): the instances with compile-time LDS strides
 void launch_tile_group(const DBatch& B, bool tabg, int mesh_kind, bool small, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters, unsigned gen);
-// workgroups of that k_tile_steps instance one CU keeps resident at `lds` bytes of dynamic LDS
-long long tile_workgroups_per_cu(int tabg, int mesh_kind, size_t lds);
 // threads of a tile's workgroup (the host sizes launches and LDS with the kernel's own constants)
 int tile_threads();
-#ifdef VXH_PAIR
-// k_robot_pair<TABG, SEL> (kernels_pair.hpp; developer library only)
-void launch_pair_group(const DBatch& B, bool tabg, bool sel, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters);
-#endif
 
 }  // namespace vxh

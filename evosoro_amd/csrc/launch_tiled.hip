@@ -1,6 +1,4 @@
 // k_tile_steps: one translation unit (launch.hpp)
-#include <algorithm>
-#include <cstdio>
 #include <cstdlib>
 #include <mutex>
 #include <string>
@@ -9,7 +7,7 @@
 
 namespace vxh {
 
-// (one table of granted dynamic-LDS sizes per kernel instance, shared by the launch and by the occupancy query: the limit only ever grows)
+// (one table of granted dynamic-LDS sizes per kernel instance: the limit only ever grows)
 template <bool TABG, bool MESH, bool FLUID, bool SMALL>
 static size_t (&granted_lds())[64] { static size_t table[64] = {}; return table; }
 
@@ -72,34 +70,5 @@ void launch_tile_group(const DBatch& B, bool tabg, int mesh_kind, bool small, co
 }
 
 int tile_threads() { return VXH_TILE_THREADS; }
-
-// Workgroups of a k_tile_steps instance one CU keeps resident at `lds` bytes of dynamic LDS.  All tiles of a robot spin on each other, so
-// an over-estimate ends in VXH_ROBOT_SYNC_TIMEOUT replays, an under-estimate only in smaller launches: the runtime's occupancy figure
-// (queried with the kernel's dynamic-LDS limit already raised to `lds`, or it answers for the 64 KB default) is clamped to ONE -- four
-// wavefronts of up to 512 registers each fill the register files of a CU whatever the LDS says (round 6; rounds 2-5: five wavefronts of
-// 256, "two per CU by the registers" was already one in practice) -- and a failing query is reported once instead of silently read as 1.
-template <bool TABG, bool MESH, bool FLUID, bool SMALL>
-static int occupancy_of(size_t lds)
-{
-    grant_dynamic_lds((const void*)k_tile_steps<TABG, MESH, FLUID, SMALL>, granted_lds<TABG, MESH, FLUID, SMALL>(), lds);
-    int n = 0;
-    const hipError_t err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)k_tile_steps<TABG, MESH, FLUID, SMALL>, VXH_TILE_THREADS, lds);
-    if (err != hipSuccess) {
-        (void)hipGetLastError();
-        static bool told = false;
-        if (!told) { told = true; std::fprintf(stderr, "vxhip: hipOccupancyMaxActiveBlocksPerMultiprocessor(k_tile_steps, %zu B of LDS) failed (%s): one workgroup per CU assumed\n", lds, hipGetErrorString(err)); }
-        return 1;
-    }
-    return n;
-}
-
-long long tile_workgroups_per_cu(int tabg, int mesh, size_t lds)
-{
-    // (the generic instances answer for their SMALL twins: same threads, same register budget)
-    const int n = mesh == 2 ? (tabg ? occupancy_of<true, true, true, false>(lds) : occupancy_of<false, true, true, false>(lds))
-                : mesh == 1 ? (tabg ? occupancy_of<true, true, false, false>(lds) : occupancy_of<false, true, false, false>(lds))
-                            : (tabg ? occupancy_of<true, false, false, false>(lds) : occupancy_of<false, false, false, false>(lds));
-    return std::min(1, std::max(1, n));
-}
 
 }  // namespace vxh

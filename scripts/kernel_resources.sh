@@ -1,6 +1,6 @@
 #!/bin/bash
 # registers / scratch / occupancy of every kernel of the engine, as the compiler reports them (no GPU needed)
-# usage: scripts/kernel_resources.sh [-f family] [extra hipcc flags]     family: engine | launch_fused_land | launch_fused_mesh | launch_wide | launch_tiled | launch_pair (default: all)
+# usage: scripts/kernel_resources.sh [-f family] [extra hipcc flags]     family: engine | launch_fused_land | launch_fused_mesh | launch_wide | launch_tiled (default: all)
 cd "$(dirname "$0")/../evosoro_amd/csrc"
 FAMS="engine launch_fused_land launch_fused_mesh launch_wide launch_tiled"
 if [ "$1" = "-f" ]; then FAMS="$2"; shift 2; fi

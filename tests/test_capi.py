@@ -128,13 +128,14 @@ def test_every_engine_option_is_documented_in_the_header():
     import re
     root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
     src = open(os.path.join(root, "evosoro_amd", "csrc", "engine.hip")).read()
-    body = src[src.index("void Engine::check_option("):]          # (set_option validates through it: every key appears there)
-    body = body[:body.index("\n}\n")]
-    keys = set(re.findall(r'key == "([a-z_]+)"', body))
-    assert {"tiled", "tile_small", "steps_per_launch", "fused"} <= keys          # (the parse found the function)
+    body = src[src.index("const OptionDesc option_table[] = {"):]          # (check_option and set_option know no key but those of the table, and "dbg")
+    body = body[:body.index("\n};\n")]
+    keys = set(re.findall(r'^ *\{"([a-z_]+)", +&Options::', body, re.M))
+    assert len(keys) == body.count("\n") and not re.search(r'key == "(?!dbg")', src)          # (one key per row, and none outside the table)
+    assert {"tiled", "tile_small", "steps_per_launch", "fused"} <= keys          # (the parse found the table)
     header = open(os.path.join(root, "include", "vxhip.h")).read()
     doc = header[header.index("/* Options (all have working defaults):"):header.index("int  vxh_set_option(")]
     missing = sorted(k for k in keys - {"dbg"} if '"%s"' % k not in doc)
     assert not missing, "options accepted by the engine but not documented in include/vxhip.h: %s" % missing
-    default = re.search(r"int steps_per_launch_ = (\d+);", open(os.path.join(root, "evosoro_amd", "csrc", "engine.hpp")).read()).group(1)
+    default = re.search(r"int steps_per_launch = (\d+);", open(os.path.join(root, "evosoro_amd", "csrc", "engine.hpp")).read()).group(1)
     assert re.search(r'"steps_per_launch".*\(default %s\)' % default, doc), "the header's default of steps_per_launch is not %s" % default

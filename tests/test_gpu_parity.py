@@ -1234,23 +1234,13 @@ def test_the_second_pose_tile_of_the_wide_kernel_changes_no_bit(eng_mod, golden_
             assert all(a[k] == b[k] for k in a if k != "reserved"), n
 
 
-def test_pair_kernel_steps_like_the_resident_kernels(eng_mod, tmp_path, kernel_path, monkeypatch):
-    """k_robot_pair (option pair: 512 threads, two voxels and up to two bonds per axis per lane; off by default since it measured slower)
-    adds the bond forces in the order of k_robot_steps<1024> -- +X and -X, then +Y, -Y, +Z, -Z -- so a robot of 769-1024 voxels must
-    come out BIT FOR BIT as that kernel steps it, self-collision, broad-phase runs and the IniCM latch included; a robot of 513-768
-    voxels (pair = 2) within the 1e-12 voxel the kernels of different summation order agree to.  Also against the oracle."""
+def test_large_resident_robots_step_the_same_in_two_calls_as_in_one(eng_mod, tmp_path, kernel_path):
+    """Robots of 513-1024 voxels on the resident kernels (k_robot_steps<768> and <1024>; tiled = 0), self-collision, broad-phase runs and the
+    IniCM latch included: 300 steps taken as 120 + 180 -- the second call reads back the saved image of the contact rows and the bond
+    history the first one left -- must give every voxel of every robot BIT FOR BIT as one call of 300 steps in a fresh engine, one robot
+    of exactly 1024 voxels (the last slot of the largest size class) among them.  Also against the oracle."""
     if kernel_path != "auto":
         pytest.skip("the test sets the kernel options itself")
-    # round 6: the kernel is compiled into the developer library only (-DVXH_PAIR, `make prof`); libvxhip.so refuses the option
-    with eng_mod.Engine(eng_mod.VOXCAD, 0) as eng:
-        with pytest.raises(eng_mod.VxhError):
-            eng.set_option("pair", 1)
-        eng.set_option("pair", 0)
-    dev_lib = os.path.join(os.path.dirname(eng_mod.LIB_PATH), "libvxhip_prof.so")
-    if not os.path.exists(dev_lib):
-        pytest.skip("developer library not built (make -C evosoro_amd/csrc prof)")
-    monkeypatch.setattr(eng_mod, "LIB_PATH", dev_lib)
-    monkeypatch.setattr(eng_mod, "_lib", None)
     from evosoro_amd import workloads
     from evosoro_amd.base import Sim, Env
     from oracle import vxoracle as vo
@@ -1261,35 +1251,89 @@ def test_pair_kernel_steps_like_the_resident_kernels(eng_mod, tmp_path, kernel_p
     mats[2][:5, :5, 10] = 1
     mats[2][0, 0, 10] = 0                                    # 1024 voxels exactly
     paths = [_write_robot(tmp_path, k, m, sim, env, "pr") for k, m in enumerate(mats)]
-    runs = {}
-    for pair in (0, 2):
+    runs = []
+    for pieces in ((120, 180), (300,)):                      # (past InitCmTime; two launches: the saved image of the contact rows is read back)
         with eng_mod.Engine(eng_mod.VOXCAD, 0) as eng:
             eng.set_option("tiled", 0)
-            eng.set_option("pair", pair)
             for p in paths:
                 eng.add_vxa_file(p)
             assert [eng.dims(i)["nvox"] for i in range(4)][2] == 1024
-            out = []
-            for n in (120, 180):                            # (past InitCmTime; two launches: the saved image of the contact rows is read back)
+            for n in pieces:
                 eng.step(n)
-                out.append([eng.state(i) for i in range(4)])
-            runs[pair] = (out, [eng.result(i).col_rebuilds for i in range(4)], [eng.result(i).as_dict() for i in range(4)])
-    for k in range(2):
-        for i in range(3):
-            assert np.array_equal(runs[0][0][k][i], runs[2][0][k][i]), (k, i)
-        assert np.abs(runs[0][0][k][3][:, :3] - runs[2][0][k][3][:, :3]).max() / 0.01 < 1e-12
-    assert runs[0][1] == runs[2][1] and min(runs[0][1]) >= 1
-    for i in range(3):
-        assert runs[0][2][i] == runs[2][2][i]               # every result field, IniCM included
+            runs.append(([eng.state(i) for i in range(4)], [eng.result(i).col_rebuilds for i in range(4)], [eng.result(i).as_dict() for i in range(4)]))
+    for i in range(4):
+        assert np.array_equal(runs[0][0][i], runs[1][0][i]), i
+        assert runs[0][2][i] == runs[1][2][i], i            # every result field, IniCM included
+    assert runs[0][1] == runs[1][1] and min(runs[0][1]) >= 1
     sim_o = vo.OracleSim.from_vxa(paths[1])
     sim_o.step(300)
-    assert _pos_err(runs[2][0][1][1], sim_o.state(), 0.01) < FLOOR_VOX
+    assert _pos_err(runs[0][0][1], sim_o.state(), 0.01) < FLOOR_VOX
+
+
+def test_option_table(eng_mod, golden_dir, kernel_path):
+    """vxh_set_option, key by key: which values are refused (VXH_ERR_ARG, -1), which keys are unknown (-1 too), and what a batch that has
+    stepped still accepts: an option that is part of the assembled batch only at the value it has (VXH_ERR_STATE, -6, otherwise -- judged
+    BEFORE the value's range, and after the value's coercion to what would be stored), the others always; after a reset, everything."""
+    if kernel_path != "auto":
+        pytest.skip("the test sets the kernel options itself")
+
+    def status(eng, key, val):
+        try:
+            eng.set_option(key, val)
+        except eng_mod.VxhError as e:
+            return e.status
+        return 0
+
+    nan = float("nan")
+    refused = [("shape_descriptors", (2, -1, 0.5, nan)), ("steps_per_launch", (0, 0.5, -3, 200001, nan)), ("graph_steps", (-1, 1000001, nan)),
+               ("wide", (2, -1, 0.5, nan)), ("wide_two_tiles", (2, -1, 0.5, nan)), ("fused", (2, -1, 0.5, nan)), ("tile_small", (2, -1, 0.5, nan)),
+               ("col_cap", (-1, 1000001, nan)), ("tiled", (3, -1, 0.5, 1.5, nan)), ("tiles_per_robot", (-1, 4097, nan))]
+    accepted = [("host_results", (1, 2, -1, 0.5, 0)), ("shape_descriptors", (1, 0)), ("steps_per_launch", (1, 1.5, 200000, 1024)), ("graph_steps", (0, 1000000, 32)),
+                ("wide", (0, 1)), ("wide_two_tiles", (0, 1)), ("fused", (0, 1)), ("tile_small", (1, 0)), ("col_cap", (1000000, 7.9, 0)),
+                ("tiled", (0, 2, 1)), ("tiles_per_robot", (4096, 3.7, 0))]           # (the last value of each: the default)
+    batch_now = [("tiled", 1), ("tiles_per_robot", 0), ("tile_small", 0), ("wide", 1), ("wide_two_tiles", 1), ("col_cap", 0), ("fused", 1)]
+    batch_other = [("tiled", 0), ("tiled", 2), ("tiles_per_robot", 3), ("tile_small", 1), ("wide", 0), ("wide_two_tiles", 0), ("col_cap", 7), ("fused", 0)]
+    with eng_mod.Engine(eng_mod.VOXCAD, 0) as eng:
+        eng.add_vxa_file(os.path.join(golden_dir, "vxa", "rand6_col.vxa"))
+        for key, vals in refused:
+            for v in vals:
+                assert status(eng, key, v) == -1, (key, v)
+        for key in ("pair", "pair_sel", "dbg", "tile", "Wide", "wide ", ""):          # (dbg: the developer library's)
+            for v in (0, 1):
+                assert status(eng, key, v) == -1, (key, v)
+        for key, vals in accepted:
+            for v in vals:
+                assert status(eng, key, v) == 0, (key, v)
+        eng.step(1)
+        assert eng.counters().dominant_block == 513            # (the defaults are back: the wide kernel)
+        for key, v in batch_now:
+            assert status(eng, key, v) == 0, (key, v)
+        for key, v in batch_other:
+            assert status(eng, key, v) == -6, (key, v)
+        # the state is judged first, on the coerced value: flags by != 0, integers truncated
+        for key, v, want in (("tiled", 5, -6), ("tiles_per_robot", 5000, -6), ("col_cap", -1, -6), ("fused", nan, -1),
+                             ("wide", 2, -1), ("tile_small", 0.5, -6), ("tiled", 1.5, -1), ("col_cap", 0.9, 0), ("tiles_per_robot", 0.9, 0)):
+            assert status(eng, key, v) == want, (key, v)
+        for key, v in (("steps_per_launch", 7), ("graph_steps", 0), ("host_results", 1), ("host_results", 0), ("shape_descriptors", 0)):
+            assert status(eng, key, v) == 0, (key, v)
+        assert status(eng, "steps_per_launch", 0) == -1 and status(eng, "graph_steps", -1) == -1
+        eng.step(1)
+        assert eng.result(0).steps == 2 and eng.counters().dominant_block == 513      # (nothing refused took effect)
+        eng.reset()
+        for key, v in batch_other:
+            assert status(eng, key, v) == 0, (key, v)
+        for key, v in batch_now:
+            if key not in ("tiled", "wide"):
+                assert status(eng, key, v) == 0, (key, v)
+        assert status(eng, "tiled", 0) == 0
+        eng.step(1)
+        assert eng.result(0).steps == 1 and eng.counters().dominant_block == 256      # (tiled = 0, wide = 0 took effect: k_robot_steps<256>)
 
 
 def test_kernel_choice_options_are_part_of_the_assembled_batch(eng_mod, golden_dir, kernel_path):
     """Which kernel steps a robot decides where its bond history lives (the resident / wide kernels keep 48-byte records of their own, and a
-    saved image of the contact rows; the streaming / tiled ones the planes): once a step has been taken, `fused`, `pair`, `wide`, `tiled`
-    are refused (VXH_ERR_STATE) instead of silently handing a robot another kernel's stale history (round-4 advisor finding for `fused`);
+    saved image of the contact rows; the streaming / tiled ones the planes): once a step has been taken, `fused`, `wide`, `wide_two_tiles`,
+    `tiled`, `tile_small`, `tiles_per_robot` and `col_cap` are refused (VXH_ERR_STATE) instead of silently handing a robot another kernel's stale history (round-4 advisor finding for `fused`);
     right after a reset they are accepted, and an unchanged value is always fine."""
     if kernel_path != "auto":
         pytest.skip("the test sets the kernel options itself")
@@ -1297,9 +1341,10 @@ def test_kernel_choice_options_are_part_of_the_assembled_batch(eng_mod, golden_d
         eng.add_vxa_file(os.path.join(golden_dir, "vxa", "rand6_col.vxa"))
         eng.set_option("fused", 1)
         eng.step(10)
-        for key, val in (("fused", 0), ("pair", 1), ("wide", 0), ("tiled", 0)):
-            with pytest.raises(eng_mod.VxhError):
+        for key, val in (("fused", 0), ("wide_two_tiles", 0), ("wide", 0), ("tiled", 0), ("tile_small", 1), ("col_cap", 7), ("tiles_per_robot", 3)):
+            with pytest.raises(eng_mod.VxhError) as refusal:
                 eng.set_option(key, val)
+            assert refusal.value.status == -6, key          # (VXH_ERR_STATE: for the state of the batch, not for an unknown name)
         eng.set_option("fused", 1)              # unchanged: accepted, the batch stays
         before = eng.state(0)
         eng.step(10)

@@ -31,6 +31,9 @@ enum RobotFlags { RF_SELF_COL = 1, RF_GRAV = 2, RF_FLOOR = 4, RF_TEMP = 8, RF_ST
 enum { VXH_ORDER_MAX_STEPS = 128,    // launches of at most this many steps are dispatched "robots due for a broad-phase run first" (kernels_fused.hpp)
        VXH_ORDER_HORIZON = 32 };     // ... and what a longer launch calls "due" when it leaves the flags for the launch behind it
 enum { VXH_RIMG_CAP = 2048 };        // entries of a saved contact-row image (the LDS pool holds at most 24 KB / 12 B)
+enum { VXH_FUSED_STATIC_LDS = 480 }; // resident kernel (kernels_fused.hpp): upper bound of its static __shared__ variables
+enum { VXH_WIDE_REC = 13,            // wide kernel (kernels_wide.hpp): doubles of a bond record in LDS
+       VXH_WIDE_STATIC_LDS = 480 };  // ... and the upper bound of its static __shared__ variables
 
 struct DRobot {               // constant per robot
     int vox_begin, nvox, surf_begin, nsurf, flags, stop_type, excl_wpr;

@@ -1,4 +1,4 @@
-// Engine implementation: batch assembly, HBM upload, step-round launches (hipGraph), download.
+// Engine implementation: HBM upload, step-round launches (hipGraph), download.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,6 +16,7 @@
 #include <stdexcept>
 #include <thread>
 
+#include "batch.hpp"
 #include "engine.hpp"
 #include "kernels.hpp"
 #include "launch.hpp"
@@ -39,24 +40,38 @@ struct Engine::Device {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // fused path: robots grouped by kernel variant (workgroup size 256/512/768/1024, exchange buffers, fluid), one
     // stream per group so that the groups fill the chip together
-    struct Group {
-        int block = 0, nacc = 0, fluid = 0, tabg = 0;   // template arguments of k_robot_steps
-        int wide = 0;                     // 1: k_robot_wide<block, fluid, tabg> (kernels_wide.hpp)
-        int two_tiles = 0;                // wide kernel: a second pose tile in LDS (two barriers per step instead of three)
-        int count = 0;
+    struct Group : GroupPlan {            // (batch.hpp: the kernel variant, its robots sorted, LDS bytes) + the HIP side
+        explicit Group(GroupPlan&& p) : GroupPlan(std::move(p)) {}
         const int* list = nullptr;
         // dispatch order of short launches (kernels_fused.hpp fused_dispatch_slot): one bit per list entry, written by a launch for the next
         unsigned long long* order_bits[2] = {nullptr, nullptr};
         int order_cur = 0;
-        bool order_valid = false, order_use = false;
-        size_t lds = 0;                   // dynamic LDS bytes
+        bool order_valid = false;
         hipStream_t stream = nullptr;
         hipEvent_t t0 = nullptr, t1 = nullptr;
-        std::vector<int> robots;
     };
     std::vector<Group> groups;
     std::vector<hipStream_t> group_streams;   // created on demand, reused across prepare() calls
     std::vector<hipEvent_t> group_events;
+    void give_stream(Group& g, size_t gi)     // the gi-th group of a batch: its stream and events
+    {
+        if (group_streams.size() <= gi) {
+            hipStream_t st; hipEvent_t e0, e1;
+            // launch groups of one call are meant to run side by side (two size classes of one population: 64 + 64 workgroups on 256
+            // CUs).  Streams share a few hardware queues, handed out round robin as streams are created: two group streams that
+            // land on the same queue run their kernels one after the other (measured: the same 64 robots of two size classes
+            // 14.8 or 24.3 us per step, depending on how many streams the process had created before).  Streams of different
+            // priority never share a queue, so the group streams cycle through the priorities the device offers.
+            int least = 0, greatest = 0;
+            HIP_OK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+            const int span = least - greatest + 1;                 // (numerically: greatest priority = smallest number)
+            const int prio = span > 1 ? greatest + (int)(group_streams.size() % (size_t)span) : 0;
+            HIP_OK(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, prio));
+            HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1));
+            group_streams.push_back(st); group_events.push_back(e0); group_events.push_back(e1);
+        }
+        g.stream = group_streams[gi]; g.t0 = group_events[2 * gi]; g.t1 = group_events[2 * gi + 1];
+    }
     const unsigned char* streamed_all = nullptr;    // masks for DBatch::streamed: every robot / the robots outside the launch groups
     const unsigned char* streamed_rest = nullptr;
     int n_rest = 0, n_all = 0;            // robots (with voxels) that only the streaming kernels can step / that they step with fused = 0
@@ -76,12 +91,9 @@ struct Engine::Device {
     int graph_rounds = 0;
     int max_nvox = 0;                     // largest robot of the batch (selects the fused block size)
     // tiled path: the robots cut into tiles, packed into launches that fit the chip (all tiles of a robot in one launch)
-    struct TileLaunch {
-        int tabg = 0, mesh = 0, count = 0;   // template arguments of k_tile_steps (mesh: land_water robots, whose strains are part of the state)
-        int small = 0;                    // ... and SMALL: every tile of the launch within VXH_TILE_S_* (compile-time LDS strides)
+    struct TileLaunch : TileLaunchPlan {  // (batch.hpp: the kernel variant, tile ids, robots, LDS bytes)
+        explicit TileLaunch(TileLaunchPlan&& p) : TileLaunchPlan(std::move(p)) {}
         const int* list = nullptr;        // tile ids
-        size_t lds = 0;
-        std::vector<int> tile_ids, robots;
     };
     std::vector<TileLaunch> tile_launches;
     std::vector<unsigned char> robot_tiled;   // per robot
@@ -607,91 +619,9 @@ struct HostStages {
 };
 }
 
-// Which kernel steps which robot: functions of the robot alone (and of the engine's options), never of the batch.
-namespace {
-// Wide kernel (kernels_wide.hpp; robots of up to WIDE_BLOCK voxels and 1023 bonds): its bond records share their LDS region with
-// the scratch of the whole-robot passes (12 * BLOCK doubles, then the mesh vertices of a robot in a fluid); the record that stays
-// zero lies behind both.
-constexpr int WIDE_BLOCK = 512;
-struct WideLayout { int zidx = 0, region = 0; };
-WideLayout wide_layout(const RobotModel& M, int variant)
-{
-    WideLayout W;
-    const bool in_fluid = variant == 1 && M.vxa.fluid_env;
-    const int scratch = 12 * WIDE_BLOCK + (in_fluid ? 3 * ((M.nvox + 63) / 64 * 64) + 3 * M.nmv : 0);
-    W.zidx = std::max(M.nbond, (scratch + VXH_WIDE_REC - 1) / VXH_WIDE_REC);
-    W.region = (VXH_WIDE_REC * (W.zidx + 1) + 1) & ~1;
-    return W;
-}
-bool wide_listed(const RobotModel& M, int variant, const Options& opt)
-{
-    return opt.wide && M.nvox > 0 && M.nvox <= WIDE_BLOCK && M.nbond <= 1023 && M.bond_classes.size() <= 4095 && wide_layout(M, variant).zidx <= 1023;
-}
-// workgroup size of the resident kernel for a robot of n voxels: its size class
-int resident_block(int n) { return n <= 256 ? 256 : (n <= 512 ? 512 : (n <= 768 ? 768 : 1024)); }
-
-// Resident kernel (kernels_fused.hpp) or wide kernel, one workgroup per robot: the variant follows from the robot's size, fluid, and the
-// LDS need of its own tables.  block == 0: neither takes the robot.
-struct FusedVariant { int block = 0, nacc = 0, fluid = 0, tabg = 0, wide = 0, two_tiles = 0; size_t lds = 0; };
-FusedVariant fused_variant(const RobotModel& M, int variant, const Options& opt)
-{
-    FusedVariant fv;
-    const size_t lds_max = 160 * 1024 - VXH_FUSED_STATIC_LDS;
-    const int n = M.nvox;
-    if (n == 0 || n > 1024 || M.bond_classes.size() > 4095) return fv;   // (12 class bits in a bond entry; a robot of 1024 voxels has at most 3072 bonds)
-    if (wide_listed(M, variant, opt)) {
-        // the wide kernel when its LDS layout fits (mirrors the top of k_robot_wide): pose tile, record region, class tables,
-        // the strain tile of a land_water robot, the mask + pool of the contact rows
-        const WideLayout W = wide_layout(M, variant);
-        const int mesh = M.nmv > 0 ? 1 : 0;
-        auto wneed = [&](bool tables_in_lds) {
-            return (size_t)(8 * WIDE_BLOCK + W.region) * 8 +
-                   (tables_in_lds ? M.bond_classes.size() * sizeof(DBondClass) + M.vox_classes.size() * sizeof(DVoxClass) : 0) +
-                   (mesh ? (size_t)48 * WIDE_BLOCK : 0) + (M.vxa.self_col_enabled ? (size_t)8 * WIDE_BLOCK : 0);
-        };
-        const int wtabg = wneed(true) > lds_max ? 1 : 0;
-        if (wneed(!wtabg) <= lds_max) {
-            fv.block = WIDE_BLOCK; fv.nacc = 0; fv.fluid = mesh; fv.tabg = wtabg; fv.wide = 1; fv.lds = wneed(!wtabg);
-            // a second pose tile (64 B per thread) where the layout leaves room for it and, for a colliding robot, for at least
-            // 8 KB of contact rows: the step then has two workgroup barriers instead of three (kernels_wide.hpp)
-            const size_t tile = (size_t)64 * WIDE_BLOCK, rows_min = M.vxa.self_col_enabled ? (size_t)8 * 1024 : 0;
-            if (opt.wide_two_tiles && fv.lds + tile + rows_min <= lds_max) fv.two_tiles = 1;
-            const size_t room = lds_max - (fv.two_tiles ? tile : 0);
-            if (M.vxa.self_col_enabled && room > fv.lds) fv.lds += std::min<size_t>(room - fv.lds, (size_t)24 * 1024);
-            fv.lds &= ~(size_t)7;
-            if (fv.two_tiles) fv.lds += tile;
-            return fv;
-        }
-    }
-    const int block = resident_block(n);
-    const int fluid = M.nmv > 0 ? 1 : 0;      // (the MESH variants: every land_water robot carries the surface mesh)
-    const bool in_fluid = variant == 1 && M.vxa.fluid_env;
-    // LDS need: pose tile, accumulator tiles, actuation phases; class tables; the mesh vertices of a robot in a
-    // fluid; with two accumulator tiles the MESH variants also hold the strain tile (with one it stays in HBM)
-    // (mirrors the layout at the top of k_robot_steps; SLIM = the 768-thread MESH variant, phases and strains in HBM)
-    const bool slim = fluid && block == 768;
-    auto need = [&](int nacc, bool tables_in_lds) {
-        return (size_t)(8 + 6 * nacc + (slim ? 0 : 2)) * block * 8 +
-               (tables_in_lds ? M.bond_classes.size() * sizeof(DBondClass) + M.vox_classes.size() * sizeof(DVoxClass) : 0) +
-               (in_fluid ? (size_t)24 * M.nmv : 0) + ((fluid && nacc == 2 && !slim) ? (size_t)48 * block : 0);
-    };
-    // accumulator tiles: two up to 768 voxels, one for 1024; class tables in LDS unless they do not fit (per-voxel
-    // evolved stiffness makes nearly every bond a class of its own), then the TABG variant reads them from HBM
-    const int nacc = block == 1024 ? 1 : 2;
-    const int tabg = need(nacc, true) > lds_max ? 1 : 0;
-    if (need(nacc, !tabg) > lds_max) return fv;                   // (e.g. a mesh with thousands of vertices)
-    fv.block = block; fv.nacc = nacc; fv.fluid = fluid; fv.tabg = tabg; fv.lds = need(nacc, !tabg);
-    // colliding robots: what the workgroup can spare without lowering the number of workgroups a CU holds (two of the 256-thread
-    // variant, by its registers; one of the others) takes the contact rows, 12 bytes per listed pair
-    if (M.vxa.self_col_enabled) {
-        const size_t room = (block == 256 ? (size_t)80 * 1024 - VXH_FUSED_STATIC_LDS : lds_max);
-        if (room > fv.lds) fv.lds += std::min<size_t>(room - fv.lds, (size_t)24 * 1024);
-    }
-    fv.lds &= ~(size_t)7;
-    return fv;
-}
-}  // namespace
-
+// Build + upload the batch.  The host tables (assemble_batch) and the tiling / launch groups (plan_launches) are worked out in batch.cpp;
+// the plan is made while the uploads of the tables drain.  Allocations and uploads keep their order: the stream-ordered pool hands out
+// addresses in call order.
 void Engine::prepare()
 {
     HostStages hs;
@@ -700,324 +630,15 @@ void Engine::prepare()
     D.free_all();
     hs.mark("free");
     const int nr = (int)robots_.size();
-    std::vector<DVoxClass> vtab;
-    std::vector<DBondClass> btab;
-    D.h_robot.assign(nr, DRobot{});
-    D.vox_begin.assign(nr, 0);
-    D.surf_begin.assign(nr, 0);
-    int nv = 0, ns = 0;
-    D.max_planned = 0;
-    D.max_nvox = 0;
-    for (int r = 0; r < nr; ++r) {
-        D.vox_begin[r] = nv;
-        D.surf_begin[r] = ns;
-        nv += (robots_[r].nvox + 63) / 64 * 64;
-        ns += robots_[r].vxa.self_col_enabled ? robots_[r].nsurf : 0;
-        if (robots_[r].nvox > 0) D.max_planned = std::max(D.max_planned, robots_[r].planned_steps);
-        D.max_nvox = std::max(D.max_nvox, robots_[r].nvox);
-    }
-    if (nv == 0) nv = 64;
-    // the kernels address a component plane as 32-bit `plane * nv + slot` (up to 36 planes of bond slots)
-    if ((long long)nv * 36 >= (1LL << 32))
-        throw std::invalid_argument("batch too large for one engine (" + std::to_string(nv) + " voxel slots; limit 119 million): split the population");
-    D.total_surf = ns;
-    long long col_total = 0;
-    // centre-of-mass traces (<TimeBetweenTraces>): one entry at most every trace_dt of simulated time after InitCmTime
-    D.trace_begin.assign(nr, 0); D.trace_cap.assign(nr, 0); D.total_trace = 0;
-    for (int r = 0; r < nr; ++r) {
-        const RobotModel& M = robots_[r];
-        D.trace_begin[r] = D.total_trace;
-        if (variant_ == 0 && M.vxa.time_between_traces > 0 && M.nvox > 0) {
-            const double span = std::max(0.0, (double)M.planned_steps * M.dt - M.vxa.init_cm_time);
-            const double n = span / M.vxa.time_between_traces + 8;
-            if (!(n < 4e6)) throw std::invalid_argument("TimeBetweenTraces asks for more than 4 million trace points");
-            D.trace_cap[r] = (int)n;
-            D.total_trace += D.trace_cap[r];
-        }
-    }
-
-    std::vector<int> wave_robot(nv / 64, -1), nbr((size_t)6 * nv, -1), surf(std::max(ns, 1), 0), surf_code(std::max(ns, 1), 0), surf_ord(nv, -1);
-    std::vector<unsigned long long> excl;
-    std::vector<unsigned short> vclass(nv, 0);
-    std::vector<short> bclass((size_t)3 * nv, -1);
-    // bond schedules of the resident kernel: [3][block] per robot, block = the workgroup size of the robot's size class
-    std::vector<int> sched_off(nr + 1, 0);
-    for (int r = 0; r < nr; ++r)
-        sched_off[r + 1] = sched_off[r] + ((robots_[r].nvox > 0 && robots_[r].nvox <= 1024) ? 3 * resident_block(robots_[r].nvox) : 0);
-    std::vector<int> bsched(std::max(sched_off[nr], 1), -1);
-    std::vector<int> wgather((size_t)2 * nv, 0);
-    std::vector<float> amp_damp(nv, 1.f);
-    std::vector<double> act_sb(nv, 0.0), act_cb(nv, 1.0);
-    bool any_dev = false;
-    for (int r = 0; r < nr; ++r) any_dev = any_dev || robots_[r].development;
-    std::vector<float> dev(any_dev ? (size_t)7 * nv : 7, 0.f);
-    std::vector<double> px(nv, 0), py(nv, 0), pz(nv, 0), sc(nv, 0), qw(nv, 1.0);
-    std::vector<unsigned char> small((size_t)3 * nv, 1);
-    // land_water robots: deformable surface mesh (fluid drag, RobotVolume tags)
-    int total_mv = 0;
-    std::vector<int> mv_begin(nr, 0);
-    bool any_mesh = false;
-    for (int r = 0; r < nr; ++r) { mv_begin[r] = total_mv; total_mv += robots_[r].nmv; any_mesh = any_mesh || robots_[r].nmv > 0; }
-    std::vector<int> vert_pack((size_t)3 * std::max(total_mv, 1), 0);
-    // robots in a fluid: the same mesh with global indices for the streaming kernels (robots that do not fit the resident one)
-    bool any_fluid = false;
-    for (int r = 0; r < nr; ++r) any_fluid = any_fluid || (variant_ == 1 && robots_[r].vxa.fluid_env && robots_[r].nmv > 0);
-    std::vector<int> vert_vox(any_fluid ? (size_t)8 * std::max(total_mv, 1) : 8, -1), vert_robot(any_fluid ? std::max(total_mv, 1) : 1, 0);
-    std::vector<double> vert_v0((size_t)3 * std::max(total_mv, 1), 0.0);
-    int total_facet = 0;
-    std::vector<int> facet_begin(nr, 0);
-    for (int r = 0; r < nr; ++r) { facet_begin[r] = total_facet; total_facet += (int)robots_[r].facet_vox.size(); }
-    std::vector<int> facet_vox(std::max(total_facet, 1), 0), facet_vert((size_t)3 * std::max(total_facet, 1), 0), facet_first(any_mesh ? nv : 1, 0);
-    std::vector<unsigned char> facet_count(any_mesh ? nv : 1, 0);
-    std::vector<int> facet_robot(any_fluid ? std::max(total_facet, 1) : 1, 0);
-    std::vector<DRobotState> rstate(nr);
-
-    // offsets of the per-robot pieces of the shared tables, then the robots are assembled on the host cores (disjoint ranges)
-    std::vector<int> vtab_off(nr + 1, 0), btab_off(nr + 1, 0), wl_off(nr + 1, 0);
-    std::vector<long long> excl_off(nr + 1, 0), col_off(nr + 1, 0);
-    std::vector<int> col_cap(nr, 0);
-    std::vector<int> img_idx(nr, -1);          // slot of the robot's saved contact-row image (DBatch::rimg_*), colliding robots of up to 1024 voxels
-    { int n_img = 0; for (int r = 0; r < nr; ++r) if (robots_[r].vxa.self_col_enabled && robots_[r].nvox > 0 && robots_[r].nvox <= 1024) img_idx[r] = n_img++; }
-    // contact rows: as long as the physics makes them -- a surface voxel can list every other one (CreateColBond, VX_Sim.cpp:753-769,
-    // has no cap) -- unless the option col_cap bounds them; 12-16 bytes per entry, untouched beyond the partners a row really has.
-    // That is nsurf^2 entries of address space per robot (75 MB for a 20^3 lattice, 1.5 GB for 512 robots of 10^3: nothing on this
-    // device), but it grows with the FOURTH power of a lattice's edge: when the uncapped rows of a batch would take more than a third of
-    // the device's free memory (a lattice of 100^3 and beyond) every robot's rows are cut to an equal share of that third, never
-    // below 64, and the engine says so -- a row that then overflows gives its robot VXH_ROBOT_COL_OVERFLOW, as with a col_cap of the
-    // user's.  (Round 3 allocated nsurf^2 whatever the size and ran out of memory in this function for lattices it used to step.)
-    long long row_limit = 0x7fffffff;
-    if (opt_.col_cap <= 0) {
-        double want = 0, rows = 0;
-        for (int r = 0; r < nr; ++r) if (robots_[r].vxa.self_col_enabled) { want += 16.0 * (double)robots_[r].nsurf * (double)std::max(1, robots_[r].nsurf - 1); rows += robots_[r].nsurf; }
-        // (the budget is a third of the device's TOTAL memory, not of what happens to be free: how long a row can grow -- and with it whether a
-        // robot ends FINISHED or COL_OVERFLOW -- must not depend on what other processes hold on the GPU at this moment; if the rows then do
-        // not fit what IS free, the allocation fails with an error instead of changing outcomes silently.  ADVICE round 4)
-        size_t free_b = 0, total_b = 0;
-        if (want > 0 && hipMemGetInfo(&free_b, &total_b) == hipSuccess && want > (double)total_b / 3.0) {
-            row_limit = std::max<long long>(64, (long long)((double)total_b / 3.0 / 16.0 / std::max(1.0, rows)));
-            std::fprintf(stderr, "vxhip: the contact rows of this batch would take %.1f GB uncapped (device memory: %.1f GB); rows are cut to %lld partners "
-                                 "(option col_cap sets the length; a robot whose row overflows ends with status COL_OVERFLOW)\n", want / 1e9, (double)total_b / 1e9, row_limit);
-        }
-    }
-    for (int r = 0; r < nr; ++r) {
-        const RobotModel& M = robots_[r];
-        if (M.vox_classes.size() > 32767 || M.bond_classes.size() > 32767) throw std::runtime_error("too many distinct voxel/bond classes in one robot");
-        vtab_off[r + 1] = vtab_off[r] + (int)M.vox_classes.size();
-        btab_off[r + 1] = btab_off[r] + (int)M.bond_classes.size();
-        excl_off[r + 1] = excl_off[r] + (M.vxa.self_col_enabled ? (long long)M.nsurf * ((M.nsurf + 63) / 64) : 0);
-        col_cap[r] = M.vxa.self_col_enabled ? std::max(1, opt_.col_cap > 0 ? std::min(opt_.col_cap, M.nsurf - 1) : (int)std::min<long long>(row_limit, M.nsurf - 1)) : 0;
-        col_off[r + 1] = col_off[r] + (long long)col_cap[r] * (M.vxa.self_col_enabled ? M.nsurf : 0);
-        wl_off[r + 1] = wl_off[r] + (wide_listed(M, variant_, opt_) ? M.nbond : 0);
-    }
-    std::vector<int> wlist(std::max(wl_off[nr], 1), -1);
-    col_total = col_off[nr];
-    vtab.resize(vtab_off[nr]);
-    btab.resize(btab_off[nr]);
-    excl.assign((size_t)excl_off[nr], 0ull);
-    auto assemble = [&](int r) {
-        const RobotModel& M = robots_[r];
-        const VxaModel& X = M.vxa;
-        const int base = D.vox_begin[r];
-        const int vtab_begin = vtab_off[r], btab_begin = btab_off[r];
-        for (size_t i = 0; i < M.vox_classes.size(); ++i) {
-            const VoxClass& c = M.vox_classes[i];
-            DVoxClass d;
-            std::memset(&d, 0, sizeof(d));
-            d.mass = c.mass; d.mass_inv = c.mass_inv; d.inertia_inv = c.inertia_inv; d.c_lin = c.c_lin; d.c_ang = c.c_ang;
-            d.E = c.E; d.k_floor = c.k_floor; d.u_static = c.u_static; d.u_dynamic = c.u_dynamic; d.cte = c.cte;
-            d.nom_size = c.nom_size; d.mat = c.mat;
-            d.prenatal_k = ((double)(float)c.nom_size / c.nom_size) - 1;
-            vtab[vtab_begin + i] = d;
-        }
-        for (size_t i = 0; i < M.bond_classes.size(); ++i) {
-            const BondClass& c = M.bond_classes[i];
-            DBondClass d;
-            std::memset(&d, 0, sizeof(d));
-            const double zi = (0.5 * X.bond_damping_z) * (1.0 / M.dt), zh = 0.5 * zi;   // BondDampingZ/2 (moments: /4) over dt
-            d.L100 = 100.0 * c.L; d.a2 = c.a2; d.b1 = c.b1; d.b2 = c.b2; d.b3 = c.b3;
-            d.kf_L = c.stress_k * c.area_sum / 2 / c.L; d.strain_a1_L = c.strain_a1 / c.L; d.strain_a2_L = c.strain_a2 / c.L;
-            d.dA1 = c.sq_a1m1 * zi; d.dB1 = c.sq_b1m1 * zi; d.dF1 = c.sq_b2fm1 * zi;
-            d.dA2 = c.sq_a1m2 * zi; d.dB2 = c.sq_b1m2 * zi; d.dF2 = c.sq_b2fm2 * zi;
-            d.dT1 = c.sq_a2i1 * zh; d.dG1 = c.sq_b2fm1 * zh; d.dH1 = c.sq_b3i1 * zh;
-            d.dT2 = c.sq_a2i2 * zh; d.dG2 = c.sq_b2fm2 * zh; d.dH2 = c.sq_b3i2 * zh;
-            d.homogeneous = c.homogeneous;
-            btab[btab_begin + i] = d;
-        }
-        for (int w = base / 64; w < (base + (M.nvox + 63) / 64 * 64) / 64; ++w) wave_robot[w] = r;
-        for (int v = 0; v < M.nvox; ++v) {
-            const int g = base + v;
-            vclass[g] = (unsigned short)M.vox_class[v];
-            { const double b = (double)(2 * 3.1415926f) * (double)M.phase_offset[v]; act_sb[g] = std::sin(b); act_cb[g] = std::cos(b); }
-            amp_damp[g] = M.temp_amp_damp[v];
-            if (M.development) {
-                const float vals[7] = {M.initial_voxel_size[v], M.final_voxel_size[v], M.start_growth_time[v], M.growth_time[v],
-                                       M.phase_offset[v], M.final_phase_offset[v], M.final_temp_amp_damp[v]};
-                for (int k = 0; k < 7; ++k) dev[(size_t)k * nv + g] = vals[k];
-            }
-            px[g] = M.nom_pos[3 * v]; py[g] = M.nom_pos[3 * v + 1]; pz[g] = M.nom_pos[3 * v + 2];
-            sc[g] = M.vox_classes[M.vox_class[v]].nom_size;
-            for (int d = 0; d < 6; ++d) { int o = M.nbr[(size_t)v * 6 + d]; nbr[(size_t)d * nv + g] = o < 0 ? -1 : base + o; }
-            for (int a = 0; a < 3; ++a) { int c = M.bond_class[(size_t)v * 3 + a]; bclass[(size_t)a * nv + g] = c < 0 ? (short)-1 : (short)c; }
-        }
-        DRobot& R = D.h_robot[r];
-        R.sched_begin = sched_off[r];
-        R.img_index = img_idx[r];
-        if (M.nvox > 0 && M.nvox <= 1024 && M.bond_classes.size() <= 4095) {
-            // The resident kernel's bond schedule.  X and Z: bond j of the axis' compacted list to thread j.  Y: the kernel variants
-            // with two accumulator tiles (up to 768 threads) evaluate X and Y without a barrier between them -- an accumulator entry
-            // gets at most one X and one Y contribution per tile, both added to zero with LDS atomics, and a + b == b + a, so the sums
-            // are those of the barrier-separated rounds bit for bit -- and a wavefront's bond is a latency-bound chain (a lone
-            // wavefront issues a dependent FP64 instruction every ~7 cycles, three that share a SIMD one every ~4): the 64-bond
-            // chunks of Y are dealt to the wavefronts that X leaves idle, least-loaded SIMD first (wavefront w runs on SIMD w mod 4),
-            // so that X + Y occupy every SIMD with three to four chunk executions spread over its three wavefronts instead of
-            // two rounds of two.  The 1024-thread variant (one tile, two barrier-separated sub-steps per round) keeps Y in list order.
-            const int block = resident_block(M.nvox), nw = block / 64;
-            int* sx = &bsched[sched_off[r]], *sy = sx + block, *sz = sy + block;
-            std::vector<int> list[3];
-            for (int a = 0; a < 3; ++a)
-                for (int v = 0; v < M.nvox; ++v) {
-                    const int c = M.bond_class[(size_t)v * 3 + a];
-                    if (c >= 0) list[a].push_back((int)((unsigned)v | ((unsigned)M.nbr[(size_t)v * 6 + 2 * a] << 10) | ((unsigned)c << 20)));
-                }
-            for (size_t j = 0; j < list[0].size(); ++j) sx[j] = list[0][j];
-            for (size_t j = 0; j < list[2].size(); ++j) sz[j] = list[2][j];
-            if (block == 1024) { for (size_t j = 0; j < list[1].size(); ++j) sy[j] = list[1][j]; }
-            else {
-                const int nchx = ((int)list[0].size() + 63) / 64, nchy = ((int)list[1].size() + 63) / 64;
-                std::vector<int> simd_load(4, 0), wave_load(nw, 0), has_y(nw, 0);
-                for (int w = 0; w < nchx; ++w) { ++simd_load[w % 4]; ++wave_load[w]; }
-                for (int c = 0; c < nchy; ++c) {
-                    int best = -1;
-                    for (int w = 0; w < nw; ++w) {
-                        if (has_y[w]) continue;
-                        if (best < 0 || simd_load[w % 4] < simd_load[best % 4] ||
-                            (simd_load[w % 4] == simd_load[best % 4] && wave_load[w] < wave_load[best])) best = w;
-                    }
-                    has_y[best] = 1; ++simd_load[best % 4]; ++wave_load[best];
-                    for (int k = 0; k < 64 && (size_t)(64 * c + k) < list[1].size(); ++k) sy[64 * best + k] = list[1][(size_t)64 * c + k];
-                }
-            }
-        }
-        R.wl_begin = wl_off[r]; R.wnbond = 0; R.wzidx = 0; R.wregion = 0;
-        if (wide_listed(M, variant_, opt_)) {
-            // wide kernel: all bonds in one list, axis after axis; a bond's place in it is the number of its record, and every voxel
-            // learns the records of its six directions (+A: the bond it is the negative end of; -A: that of its -A neighbour)
-            const WideLayout W = wide_layout(M, variant_);
-            std::vector<int> slot_of((size_t)M.nvox * 3, -1);
-            int t = 0;
-            for (int a = 0; a < 3; ++a)
-                for (int v = 0; v < M.nvox; ++v) {
-                    const int c = M.bond_class[(size_t)v * 3 + a];
-                    if (c < 0) continue;
-                    slot_of[(size_t)v * 3 + a] = t;
-                    wlist[wl_off[r] + t++] = (int)((unsigned)v | ((unsigned)M.nbr[(size_t)v * 6 + 2 * a] << 9) | ((unsigned)a << 18) | ((unsigned)c << 20));
-                }
-            for (int v = 0; v < M.nvox; ++v) {
-                int idx[6];
-                for (int a = 0; a < 3; ++a) {
-                    idx[2 * a] = slot_of[(size_t)v * 3 + a];
-                    const int n = M.nbr[(size_t)v * 6 + 2 * a + 1];
-                    idx[2 * a + 1] = n >= 0 ? slot_of[(size_t)n * 3 + a] : -1;
-                }
-                for (int d = 0; d < 6; ++d) if (idx[d] < 0) idx[d] = W.zidx;
-                wgather[base + v] = idx[0] | (idx[1] << 10) | (idx[2] << 20);
-                wgather[(size_t)nv + base + v] = idx[3] | (idx[4] << 10) | (idx[5] << 20);
-            }
-            R.wnbond = M.nbond; R.wzidx = W.zidx; R.wregion = W.region;
-        }
-        if (X.self_col_enabled)
-            for (int i = 0; i < M.nsurf; ++i) {
-                surf[D.surf_begin[r] + i] = base + M.surf[i]; surf_ord[base + M.surf[i]] = i;
-                surf_code[D.surf_begin[r] + i] = (int)((unsigned)M.surf[i] | ((unsigned)M.vox_class[M.surf[i]] << 10));     // (robots the resident kernels take: < 1024 voxels)
-            }
-        // CalcNearby exclusion lists as bit rows over surface ordinals
-        const long long excl_begin = excl_off[r];
-        int wpr = 0;
-        if (X.self_col_enabled) {
-            wpr = (M.nsurf + 63) / 64;
-            std::vector<int> ord(M.nvox, -1);
-            for (int i = 0; i < M.nsurf; ++i) ord[M.surf[i]] = i;
-            for (int i = 0; i < M.nsurf; ++i) {
-                const int vi = M.surf[i];
-                for (int k = M.near_off[vi]; k < M.near_off[vi + 1]; ++k) {
-                    const int j = ord[M.near_idx[k]];
-                    if (j >= 0) excl[(size_t)excl_begin + (size_t)i * wpr + (j >> 6)] |= 1ull << (j & 63);
-                }
-            }
-        }
-        R.col_begin = col_off[r]; R.col_cap = col_cap[r];
-        R.vox_begin = base; R.nvox = M.nvox; R.surf_begin = D.surf_begin[r]; R.nsurf = X.self_col_enabled ? M.nsurf : 0;
-        R.flags = (X.self_col_enabled ? RF_SELF_COL : 0) | (X.grav_enabled ? RF_GRAV : 0) | (X.floor_enabled ? RF_FLOOR : 0) |
-                  (X.temp_enabled ? RF_TEMP : 0) | ((X.sticky_floor && variant_ == 0) ? RF_STICKY : 0) |
-                  ((variant_ == 1 && X.fluid_env) ? RF_FLUID : 0) | (variant_ == 1 ? RF_LW : 0) |
-                  ((X.col_system == 2 || X.col_system == 3) ? RF_HORIZON_COL : 0) |
-                  (M.development ? RF_DEV : 0) | ((X.has_initial_voxel_size || X.has_final_voxel_size) ? RF_DEV_SIZE : 0) |
-                  (X.has_final_voxel_size ? RF_DEV_FSIZE : 0) | (X.has_final_phase_offset ? RF_DEV_FPHASE : 0) |
-                  (X.has_final_temp_amp_damp ? RF_DEV_FTAD : 0);
-        R.stop_type = X.stop_type; R.excl_wpr = wpr; R.excl_begin = excl_begin;
-        R.vert_begin = mv_begin[r]; R.nmv = M.nmv;
-        R.facet_begin = facet_begin[r]; R.nfacet = (int)M.facet_vox.size();
-        for (size_t f = 0; f < M.facet_vox.size(); ++f) {
-            facet_vox[facet_begin[r] + f] = M.facet_vox[f];
-            if (any_fluid) facet_robot[facet_begin[r] + f] = r;
-            for (int k = 0; k < 3; ++k) facet_vert[(size_t)k * std::max(total_facet, 1) + facet_begin[r] + f] = M.facet_vert[f * 3 + k];
-        }
-        R.vtab_begin = vtab_begin; R.n_vclass = (int)M.vox_classes.size(); R.btab_begin = btab_begin; R.n_bclass = (int)M.bond_classes.size();
-        if (M.nmv > 0) {
-            const size_t tm = (size_t)std::max(total_mv, 1);
-            for (int i = 0; i < M.nmv; ++i) {
-                unsigned w[3] = {0, 0, 0};
-                for (int q = 0; q < 8; ++q) {
-                    const int c = M.vert_comp[(size_t)i * 8 + q];
-                    if (c < 0 || M.nvox > 1024) continue;       // (only the fused path, robots <= 1024 voxels, reads it)
-                    const unsigned corner = (unsigned)c & 7u, l = (unsigned)c >> 3;
-                    w[corner / 3] |= l << (10 * (corner % 3));
-                    w[2] |= 1u << (20 + corner);
-                }
-                for (int k = 0; k < 3; ++k) vert_pack[k * tm + mv_begin[r] + i] = (int)w[k];
-                if (any_fluid) {
-                    vert_robot[mv_begin[r] + i] = r;
-                    for (int q = 0; q < 8; ++q) {
-                        const int c = M.vert_comp[(size_t)i * 8 + q];
-                        if (c >= 0) vert_vox[(size_t)(c & 7) * tm + mv_begin[r] + i] = base + (c >> 3);
-                    }
-                }
-                for (int k = 0; k < 3; ++k) vert_v0[k * tm + mv_begin[r] + i] = M.vert_v0[(size_t)i * 3 + k];
-            }
-            for (int v = 0; v < M.nvox; ++v) {
-                facet_first[base + v] = M.facet_first[v]; facet_count[base + v] = M.facet_count[v];
-            }
-        }
-        R.dt = M.dt; R.lat = X.lattice_dim; R.bond_z_half = 0.5 * X.bond_damping_z; R.slow_z = X.slow_damping_z; R.col_z = X.col_damping_z;
-        R.grav_acc = X.grav_acc; R.init_cm_time = X.init_cm_time; R.stop_value = X.stop_value;
-        R.afterlife = variant_ == 0 ? X.afterlife_time : 0.0;
-        R.temp_period_d = X.temp_period; R.min_temp_fact = X.min_temp_fact; R.growth_amplitude = X.growth_amplitude;
-        R.col_horizon = X.collision_horizon;
-        { double fd = X.collision_horizon * 1.5 * X.lattice_dim; R.filter_dist2 = fd * fd; }
-        R.drag_coef = X.aggregate_drag_coef;
-        R.midlife_freeze_time = X.midlife_freeze_time;
-        R.trace_dt = D.trace_cap[r] > 0 ? X.time_between_traces : 0.0; R.trace_begin = D.trace_begin[r]; R.trace_cap = D.trace_cap[r];
-        R.temp_amplitude = (float)X.temp_amplitude; R.temp_period = (float)X.temp_period;
-        DRobotState& S = rstate[r];
-        std::memset(&S, 0, sizeof(S));
-        S.max_disp = (double)FLT_MAX;      // ClearAll, VX_Sim.cpp:369: forces a collision-list build on the first step
-        S.act_time = -1.0;
-        S.status = M.nvox == 0 ? 3 : 0;
-    };
-    {
-        std::atomic<int> next{0};
-        auto worker = [&]() { for (int r = next.fetch_add(1); r < nr; r = next.fetch_add(1)) assemble(r); };
-        const int nthreads = std::max(1, std::min({nr / 8, (int)std::thread::hardware_concurrency(), 32}));
-        std::vector<std::thread> pool;
-        for (int t = 1; t < nthreads; ++t) pool.emplace_back(worker);
-        worker();
-        for (auto& t : pool) t.join();
-    }
+    size_t free_b = 0, total_b = 0;           // (the contact-row budget; only asked for when no col_cap bounds the rows)
+    if (opt_.col_cap <= 0 && hipMemGetInfo(&free_b, &total_b) != hipSuccess) total_b = 0;
+    HostBatch H = assemble_batch(robots_, variant_, opt_, total_b);
+    const int nv = H.nv, ns = H.ns;
     hs.mark("host assembly");
     DBatch& B = D.B;
     B.n_robots = nr; B.nv = nv; B.dbg = dbg_;
-    B.robot = D.upload(D.h_robot);
-    B.rstate = D.upload(rstate);
+    B.robot = D.upload(H.robot);
+    B.rstate = D.upload(H.rstate);
     {   // ... and their mirror in pinned host memory, which the resident kernels write as well (a call that runs one launch group and
         // nothing else needs no copy back: ~10-15 us of a 0.7 ms call); start values for the robots no kernel touches
         if (D.h_rstate_cap < (size_t)nr) {
@@ -1026,26 +647,26 @@ void Engine::prepare()
             HIP_OK(hipHostMalloc((void**)&D.h_rstate, sizeof(DRobotState) * std::max(nr, 1), hipHostMallocDefault));
             D.h_rstate_cap = (size_t)std::max(nr, 1);
         }
-        std::memcpy(D.h_rstate, rstate.data(), sizeof(DRobotState) * nr);
+        std::memcpy(D.h_rstate, H.rstate.data(), sizeof(DRobotState) * nr);
         void* dp = nullptr;
         B.rstate_mirror = hipHostGetDevicePointer(&dp, D.h_rstate, 0) == hipSuccess ? (DRobotState*)dp : nullptr;
     }
-    B.wave_robot = D.upload(wave_robot);
-    B.vclass_tab = D.upload(vtab);
-    B.bclass_tab = D.upload(btab);
-    B.vclass = D.upload(vclass);
-    B.bclass = D.upload(bclass);
-    B.nbr = D.upload(nbr);
-    B.bsched = D.upload(bsched);
-    B.wlist = D.upload(wlist);
-    B.wgather = D.upload(wgather);
-    B.act_sb = D.upload(act_sb);
-    B.act_cb = D.upload(act_cb);
-    B.amp_damp = D.upload(amp_damp);
-    B.dev = D.upload(dev);
+    B.wave_robot = D.upload(H.wave_robot);
+    B.vclass_tab = D.upload(H.vtab);
+    B.bclass_tab = D.upload(H.btab);
+    B.vclass = D.upload(H.vclass);
+    B.bclass = D.upload(H.bclass);
+    B.nbr = D.upload(H.nbr);
+    B.bsched = D.upload(H.bsched);
+    B.wlist = D.upload(H.wlist);
+    B.wgather = D.upload(H.wgather);
+    B.act_sb = D.upload(H.act_sb);
+    B.act_cb = D.upload(H.act_cb);
+    B.amp_damp = D.upload(H.amp_damp);
+    B.dev = D.upload(H.dev);
     {   // vs[18][nv]: nominal position + scale in both buffers, identity quaternions, zero momenta
         double* vs = D.alloc_zero<double>((size_t)18 * nv);
-        const std::vector<double>* planes[5] = {&px, &py, &pz, &sc, &qw};
+        const std::vector<double>* planes[5] = {&H.px, &H.py, &H.pz, &H.sc, &H.qw};
         for (int k = 0; k < 5; ++k)
             HIP_OK(hipMemcpyAsync(vs + (size_t)(k < 4 ? k : 8) * nv, planes[k]->data(), sizeof(double) * nv, hipMemcpyHostToDevice, D.stream));
         HIP_OK(hipMemcpyAsync(vs + (size_t)4 * nv, vs, sizeof(double) * 4 * nv, hipMemcpyDeviceToDevice, D.stream));
@@ -1053,342 +674,97 @@ void Engine::prepare()
     }
     B.hist = D.alloc_zero<double>((size_t)6 * 3 * nv);
     B.hist_aos = D.alloc_zero<double>((size_t)6 * 3 * nv);
-    B.small_angle = D.upload(small);
+    B.small_angle = D.upload(H.small);
     B.bout = D.alloc_zero<double>((size_t)12 * 3 * nv);
-    B.surf = D.upload(surf);
-    B.surf_code = D.upload(surf_code);
-    B.surf_ord = D.upload(surf_ord);
-    B.excl = D.upload(excl);
-    B.total_mv = std::max(total_mv, 1);
-    B.vert_pack = D.upload(vert_pack);
-    B.vert_v0 = D.upload(vert_v0);
-    B.total_facet = std::max(total_facet, 1);
-    B.facet_vox = D.upload(facet_vox);
-    B.facet_vert = D.upload(facet_vert);
-    B.facet_first = D.upload(facet_first);
-    B.facet_count = D.upload(facet_count);
-    B.strain = D.alloc_zero<double>(any_mesh ? (size_t)6 * nv : 1);
-    B.n_mv = total_mv; B.n_facet = total_facet;
-    B.vert_vox = D.upload(vert_vox);
-    B.vert_robot = D.upload(vert_robot);
-    B.facet_robot = D.upload(facet_robot);
-    B.mesh_pos = D.alloc_zero<double>(any_fluid ? (size_t)3 * std::max(total_mv, 1) : 1);
-    B.fdrag = D.alloc_zero<double>(any_fluid ? (size_t)3 * std::max(total_facet, 1) : 1);
-    D.any_fluid = any_fluid;
-    B.trace = D.alloc_zero<double>((size_t)std::max(D.total_trace, 1) * 4);
+    B.surf = D.upload(H.surf);
+    B.surf_code = D.upload(H.surf_code);
+    B.surf_ord = D.upload(H.surf_ord);
+    B.excl = D.upload(H.excl);
+    B.total_mv = std::max(H.total_mv, 1);
+    B.vert_pack = D.upload(H.vert_pack);
+    B.vert_v0 = D.upload(H.vert_v0);
+    B.total_facet = std::max(H.total_facet, 1);
+    B.facet_vox = D.upload(H.facet_vox);
+    B.facet_vert = D.upload(H.facet_vert);
+    B.facet_first = D.upload(H.facet_first);
+    B.facet_count = D.upload(H.facet_count);
+    B.strain = D.alloc_zero<double>(H.any_mesh ? (size_t)6 * nv : 1);
+    B.n_mv = H.total_mv; B.n_facet = H.total_facet;
+    B.vert_vox = D.upload(H.vert_vox);
+    B.vert_robot = D.upload(H.vert_robot);
+    B.facet_robot = D.upload(H.facet_robot);
+    B.mesh_pos = D.alloc_zero<double>(H.any_fluid ? (size_t)3 * std::max(H.total_mv, 1) : 1);
+    B.fdrag = D.alloc_zero<double>(H.any_fluid ? (size_t)3 * std::max(H.total_facet, 1) : 1);
+    D.any_fluid = H.any_fluid;
+    B.trace = D.alloc_zero<double>((size_t)std::max(H.total_trace, 1) * 4);
     B.col_rows = std::max(ns, 1);
     B.col_cnt = D.alloc_zero<int>(std::max(ns, 1));
     {   // saved LDS images of the contact rows (resident kernel): one slot per colliding robot of up to 1024 voxels
         int n_img = 0;
-        for (int r = 0; r < nr; ++r) if (img_idx[r] >= 0) ++n_img;
+        for (int r = 0; r < nr; ++r) if (H.img_idx[r] >= 0) ++n_img;
         B.rimg_code = D.alloc_raw<int>((size_t)std::max(n_img, 1) * VXH_RIMG_CAP);
         B.rimg_a1 = D.alloc_raw<double>((size_t)std::max(n_img, 1) * VXH_RIMG_CAP);
         B.rimg_seg = D.alloc_zero<int>((size_t)std::max(n_img, 1) * 64);
         B.rimg_rowd = D.alloc_zero<int>((size_t)nv);
     }
-    B.col_partner = D.alloc_raw<int>((size_t)std::max<long long>(col_off[nr], 1));     // (entries beyond col_cnt are never read)
-    B.col_a1 = D.alloc_raw<double>((size_t)std::max<long long>(col_off[nr], 1));
+    B.col_partner = D.alloc_raw<int>((size_t)std::max<long long>(H.col_total, 1));     // (entries beyond col_cnt are never read)
+    B.col_a1 = D.alloc_raw<double>((size_t)std::max<long long>(H.col_total, 1));
     hs.mark("allocations + uploads");
-    // Tiled kernel (kernels_tiled.hpp), several workgroups per robot: for robots the resident kernel cannot take, and for
-    // populations too small to give every CU a robot.  The number of tiles depends on the population (the results do not:
-    // the tiled kernel's arithmetic per bond and per voxel, and its summation orders, are those of the resident kernel).
-    D.robot_tiled.assign(nr, 0);
-    D.robot_tiles.assign(nr, 0);
+    LaunchPlan P = plan_launches(robots_, H, variant_, opt_, tiling_allowed_, D.n_cu);
     D.tile_launches.clear();
-    std::vector<DTile> h_tiles;
-    std::vector<int> tile_vox, tile_bond, tile_bcls, tile_bslot, xslot(nv, 0);
-    std::vector<int> tmv_slot[8], tf_owner, tf_vert[3], tile_ffirst, tile_mvox;      // fluid tiles: mesh vertices (per corner code), facets, the voxels under the vertices
-    std::vector<double> tmv_v0[3];
-    std::vector<unsigned char> tile_fcount;
-    bool any_fluid_tiles = false;
-    int nx_total = 0;
-    const int tiled_now = tiling_allowed_ ? opt_.tiled : 0;
-    if (tiled_now > 0) {
-        const size_t lds_cap = 160 * 1024 - VXH_TILE_STATIC_LDS;
-        int n_work = 0;
-        for (int r = 0; r < nr; ++r) if (robots_[r].nvox > 0) ++n_work;
-        // Which robots are tiled.  By default only those the resident kernel cannot take (more than 1024 voxels, oversized tables): the
-        // kernel that steps a robot is then a function of the robot ALONE, and so is its trajectory, bit for bit, whatever the batch --
-        // a robot re-evaluated alone gives the bits it gave inside a generation of 512 (tests/test_gpu_parity.py
-        // test_full_size_batch_properties; the tiled and the resident kernel agree to 1e-12 voxel, not to the bit).
-        // Option tile_small = 1 gives that up for speed where it was measured to pay (scripts/dev_gpu_diag.py tilepolicy, one box, us per
-        // population step, resident | tiled): 64 robots of 6^3 10.2 | 11.1, 7^3 11.0 | 11.3, 8^3 11.1 | 11.7, 9^3 13.7 | 14.2, 10^3 15.6 |
-        // 14.7; 16 of 10^3 15.1 | 13.2; 128 of 8^3 11.3 | 14.0; 128 of 10^3 16.0 | 32.9 (their tiles no longer fit one co-resident
-        // launch) -- i.e. large robots (the 768- and 1024-thread variants) in populations of at most a quarter of the CUs.  (Until late in
-        // round 2 the default was "any robot, up to three quarters of the CUs": slower for every size below 10^3, 2x slower at 128 robots,
-        // and population-dependent in the last bits.)
-        const bool small_population = opt_.tile_small && n_work * 4 <= D.n_cu;
-        std::vector<int> cand;
-        for (int r = 0; r < nr; ++r) {
-            const RobotModel& M = robots_[r];
-            // land_water robots are tiled on land (round 4: the tiles keep the directional strains the RobotVolume tags need) and, since
-            // round 5, in a FLUID: the tile then carries its part of the drag mesh, and the voxels a mesh vertex averages over -- up to
-            // seven, across tile boundaries, diagonal neighbours included -- come through the exchange buffer with their strains
-            if (M.nvox == 0) continue;
-            const int block = fused_variant(M, variant_, opt_).block;
-            if (tiled_now == 2 || !opt_.fused || block == 0 || (small_population && block >= 768)) cand.push_back(r);
-        }
-        // tiles per robot: one bond per lane and one WAVEFRONT of owned voxels per tile if the CUs allow it (a step then costs one bond
-        // evaluation + one voxel update on one wavefront + the barrier), fewer when the candidates outnumber the CUs.  (Until late in
-        // round 3 only the bonds counted: 112 tiles of 71-72 voxels for the 20^3 lattice -- a second, nearly empty wavefront in every
-        // voxel phase -- where 125 tiles of 64 step it in 8.7 instead of 10.3 us; scripts/dev_gpu_diag.py cfg4tiles: 64 tiles 11.2,
-        // 216 tiles 9.1, 250 tiles 8.8.)
-        auto k_bonds = [&](const RobotModel& M) { return std::max(1, (int)((M.nbond * 5LL / 4 + VXH_TILE_BLOCK - 1) / VXH_TILE_BLOCK)); };
-        auto k_wave = [&](const RobotModel& M) { return std::max(k_bonds(M), (M.nvox + 63) / 64); };
-        long long sum_wave = 0;
-        for (int r : cand) sum_wave += k_wave(robots_[r]);
-        const bool by_wave = sum_wave <= D.n_cu;       // (else the round-2 rule: by bonds, scaled down to the CUs -- 64 robots of 10^3 with tile_small: 14.3 us, against 16.4 with the wavefront rule scaled down)
-        auto k_latency = [&](const RobotModel& M) { return by_wave ? k_wave(M) : k_bonds(M); };
-        long long sum_lat = 0;
-        for (int r : cand) sum_lat += k_latency(robots_[r]);
-        struct Planned { int r; TilePlan plan; int tabg; size_t lds; int mesh; int small; };
-        // a robot in a fluid: per tile the mesh vertices its owned voxels' facets use and those facets (counts, for the LDS layout; the tables
-        // themselves are filled when the exchange slots of the robot's voxels are known)
-        auto in_fluid = [&](const RobotModel& M) { return variant_ == 1 && M.vxa.fluid_env && M.nmv > 0; };
-        auto tile_mesh_counts = [&](const RobotModel& M, const TilePlan::Tile& t, int& n_mv, int& n_f, int& n_mx) {
-            n_mv = n_f = n_mx = 0;
-            if (!in_fluid(M)) return;
-            std::vector<char> seen(M.nmv, 0), vseen(M.nvox, 0);
-            for (int v : t.own)
-                for (int f = M.facet_first[v]; f < M.facet_first[v] + (int)M.facet_count[v]; ++f) {
-                    ++n_f;
-                    for (int k = 0; k < 3; ++k) {
-                        const int i = M.facet_vert[(size_t)f * 3 + k];
-                        if (seen[i]) continue;
-                        seen[i] = 1; ++n_mv;
-                        for (int e = 0; e < 8; ++e) { const int c = M.vert_comp[(size_t)i * 8 + e]; if (c >= 0 && !vseen[c >> 3]) { vseen[c >> 3] = 1; ++n_mx; } }
-                    }
-                }
-        };
-        std::vector<Planned> planned;
-        for (int r : cand) {
-            const RobotModel& M = robots_[r];
-            const int tab_doubles = (int)(M.bond_classes.size() * sizeof(DBondClass) / 8 + M.vox_classes.size() * sizeof(DVoxClass) / 8);
-            const int tabg = (size_t)tab_doubles * 8 > 32 * 1024 ? 1 : 0;
-            int k = opt_.tiles_per_robot > 0 ? opt_.tiles_per_robot
-                                         : (sum_lat <= D.n_cu ? k_latency(M) : std::max(1, (int)(k_latency(M) * (long long)D.n_cu / sum_lat)));
-            k = std::max(1, std::min(k, M.nvox / 8));
-            for (;;) {
-                TilePlan P = plan_tiles(M, k);
-                size_t lds = 0;
-                bool small = true;                                    // every tile within the SMALL size class: its kernel instances, its (fixed) layout
-                for (const auto& t : P.tiles) small = small && (int)t.own.size() <= VXH_TILE_S_OWN && (int)t.halo.size() <= VXH_TILE_S_HALO && (int)t.bond_v1.size() <= VXH_TILE_S_BONDS;
-                for (const auto& t : P.tiles) {
-                    int n_mv = 0, n_f = 0, n_mx = 0;
-                    tile_mesh_counts(M, t, n_mv, n_f, n_mx);
-                    const TileLayout TL = small ? tile_layout(VXH_TILE_S_OWN, VXH_TILE_S_HALO, VXH_TILE_S_BONDS, tabg ? 0 : tab_doubles, M.nmv > 0, n_mv, n_f, n_mx)
-                                                : tile_layout((int)t.own.size(), (int)t.halo.size(), (int)t.bond_v1.size(), tabg ? 0 : tab_doubles, M.nmv > 0, n_mv, n_f, n_mx);
-                    lds = std::max(lds, (size_t)TL.total * 8);
-                }
-                if (P.k > VXH_TILE_MAX_TILES) break;                  // (left to the other kernels)
-                if (P.max_own <= VXH_TILE_BLOCK && P.max_local <= 1024 && lds <= lds_cap) { planned.push_back({r, std::move(P), tabg, lds, M.nmv > 0 ? (in_fluid(M) ? 2 : 1) : 0, small ? 1 : 0}); break; }
-                if (k >= M.nvox / 8) break;                           // cannot be tiled: left to the other kernels
-                k = std::min(std::max(k + 1, k * 5 / 4 + 1), std::max(1, M.nvox / 8));
-            }
-        }
-        // launches: all tiles of a robot in one launch, a launch no larger than what the chip keeps resident (the tiles of a
-        // robot wait for each other): ONE workgroup per CU -- four wavefronts of up to 512 registers each fill the register files of a CU
-        // whatever the LDS says, and an over-estimate ends in VXH_ROBOT_SYNC_TIMEOUT replays, an under-estimate only in smaller launches
-        const long long capacity = D.n_cu;
-        for (int kind = 0; kind < 12; ++kind) {
-            const int tabg = kind & 1, mesh = (kind >> 1) % 3, small = kind / 6;      // mesh: 0 _voxcad, 1 land_water on land, 2 land_water in a fluid
-            Device::TileLaunch cur;
-            cur.tabg = tabg; cur.mesh = mesh; cur.small = small;
-            for (auto& q : planned) {
-                if (q.tabg != tabg || q.mesh != mesh || q.small != small) continue;
-                const int k = q.plan.k;
-                if (k > capacity) continue;                    // more tiles than the chip holds: not tiled
-                if (cur.count > 0 && cur.count + k > capacity) { D.tile_launches.push_back(cur); cur = Device::TileLaunch(); cur.tabg = tabg; cur.mesh = mesh; cur.small = small; }
-                cur.lds = std::max(cur.lds, q.lds);
-                const int tile0 = (int)h_tiles.size(), base = D.vox_begin[q.r];
-                for (int t = 0; t < k; ++t) {
-                    const TilePlan::Tile& T = q.plan.tiles[t];
-                    DTile d;
-                    d.robot = q.r; d.tile0 = tile0; d.ntiles = k;
-                    d.n_own = (int)T.own.size(); d.n_halo = (int)T.halo.size(); d.nb = (int)T.bond_v1.size();
-                    d.vox_off = (int)tile_vox.size(); d.bond_off = (int)tile_bond.size();
-                    d.xoff = nx_total; d.pad = 0; d.mv_off = d.n_mv = d.f_off = d.n_f = d.mx_off = d.n_mx = 0;
-                    for (size_t i = 0; i < T.own.size(); ++i) { tile_vox.push_back(base + T.own[i]); xslot[base + T.own[i]] = nx_total + (int)i; }
-                    nx_total += ((int)T.own.size() + 63) / 64 * 64;
-                    for (int v : T.halo) tile_vox.push_back(-(base + v) - 1);      // (exchange slots once every tile of the robot has its range)
-                    for (size_t b = 0; b < T.bond_v1.size(); ++b) {
-                        tile_bond.push_back(T.bond_entry[b]);
-                        tile_bcls.push_back(robots_[q.r].bond_class[(size_t)T.bond_v1[b] * 3 + T.bond_axis[b]]);
-                        tile_bslot.push_back(T.bond_axis[b] * nv + base + T.bond_v1[b]);
-                    }
-                    cur.tile_ids.push_back((int)h_tiles.size());
-                    h_tiles.push_back(d);
-                }
-                for (int t = 0; t < k; ++t) {                          // halo voxels: global slot -> exchange slot
-                    const DTile& d = h_tiles[tile0 + t];
-                    for (int i = 0; i < d.n_halo; ++i) { int& e = tile_vox[d.vox_off + d.n_own + i]; e = xslot[-(e + 1)]; }
-                }
-                tile_ffirst.resize(tile_vox.size(), 0); tile_fcount.resize(tile_vox.size(), 0);
-                if (in_fluid(robots_[q.r])) {
-                    // the drag mesh, tile by tile: the vertices the facets of the tile's owned voxels use (every voxel touching such a vertex named
-                    // by its EXCHANGE slot: the vertex pass reads pose and strains of all of them from the exchange buffer, whoever owns them)
-                    // and those facets, per owned voxel in the reference's order
-                    const RobotModel& M = robots_[q.r];
-                    any_fluid_tiles = true;
-                    for (int t = 0; t < k; ++t) {
-                        DTile& d = h_tiles[tile0 + t];
-                        const TilePlan::Tile& T = q.plan.tiles[t];
-                        std::vector<int> local(M.nmv, -1), verts;
-                        d.f_off = (int)tf_owner.size();
-                        for (size_t o = 0; o < T.own.size(); ++o) {
-                            const int v = T.own[o];
-                            tile_ffirst[d.vox_off + o] = (int)tf_owner.size() - d.f_off;
-                            tile_fcount[d.vox_off + o] = M.facet_count[v];
-                            for (int f = M.facet_first[v]; f < M.facet_first[v] + (int)M.facet_count[v]; ++f) {
-                                tf_owner.push_back((int)o);
-                                for (int c = 0; c < 3; ++c) {
-                                    const int i = M.facet_vert[(size_t)f * 3 + c];
-                                    if (local[i] < 0) { local[i] = (int)verts.size(); verts.push_back(i); }
-                                    tf_vert[c].push_back(local[i]);
-                                }
-                            }
-                        }
-                        d.n_f = (int)tf_owner.size() - d.f_off;
-                        d.mv_off = (int)tmv_v0[0].size(); d.n_mv = (int)verts.size();
-                        d.mx_off = (int)tile_mvox.size();
-                        std::vector<int> vlocal(M.nvox, -1);
-                        for (int i : verts) {
-                            int slot[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
-                            for (int e = 0; e < 8; ++e) {
-                                const int c = M.vert_comp[(size_t)i * 8 + e];
-                                if (c < 0) continue;
-                                const int v = c >> 3;
-                                if (vlocal[v] < 0) { vlocal[v] = (int)tile_mvox.size() - d.mx_off; tile_mvox.push_back(xslot[base + v]); }
-                                slot[c & 7] = vlocal[v];
-                            }
-                            for (int c = 0; c < 8; ++c) tmv_slot[c].push_back(slot[c]);
-                            for (int c = 0; c < 3; ++c) tmv_v0[c].push_back(M.vert_v0[(size_t)i * 3 + c]);
-                        }
-                        d.n_mx = (int)tile_mvox.size() - d.mx_off;
-                    }
-                }
-                cur.count += k;
-                cur.robots.push_back(q.r);
-                D.robot_tiled[q.r] = 1;
-                D.robot_tiles[q.r] = k;
-            }
-            if (cur.count > 0) D.tile_launches.push_back(cur);
-        }
-        for (auto& L : D.tile_launches) {
-            L.list = D.upload(L.tile_ids);
-            // a launch with no more tiles than CUs: a CU to every tile.  Two tiles that share a CU share its SIMDs, run at half
-            // speed, and the whole robot waits for them at every barrier; asking for more than half of the LDS keeps them apart.
-            if (L.count <= D.n_cu) L.lds = std::max(L.lds, (size_t)(81 * 1024));
-            if (std::getenv("VXH_PROF_TILES"))
-                std::fprintf(stderr, "vxhip: tile launch kind tabg=%d mesh=%d: %d tiles of %zu robots, %zu B of LDS, 1 workgroups per CU\n", L.tabg, L.mesh, L.count,
-                             L.robots.size(), L.lds);
-        }
+    for (auto& L : P.tile_launches) {
+        D.tile_launches.emplace_back(std::move(L));
+        D.tile_launches.back().list = D.upload(D.tile_launches.back().tile_ids);
     }
-    {
-        std::vector<int> tile_of(h_tiles.empty() ? 1 : nv, -1), tile_lidx(h_tiles.empty() ? 1 : nv, 0);
-        for (size_t t = 0; t < h_tiles.size(); ++t)
-            for (int k = 0; k < h_tiles[t].n_own; ++k) { const int g = tile_vox[h_tiles[t].vox_off + k]; tile_of[g] = (int)t; tile_lidx[g] = k; }
-        B.tile_of = D.upload(tile_of);
-        B.tile_lidx = D.upload(tile_lidx);
-        B.col_code = D.alloc_raw<int>(h_tiles.empty() ? 1 : (size_t)std::max<long long>(col_total, 1));
-        B.tile_xh = D.alloc_zero<int>(std::max<size_t>(1, h_tiles.size()) * VXH_TILE_XH);
-        B.tile_xhn = D.alloc_zero<int>(std::max<size_t>(1, h_tiles.size()));
+    const bool no_tiles = P.tiles.empty();
+    B.tile_of = D.upload(P.tile_of);
+    B.tile_lidx = D.upload(P.tile_lidx);
+    B.col_code = D.alloc_raw<int>(no_tiles ? 1 : (size_t)std::max<long long>(H.col_total, 1));
+    B.tile_xh = D.alloc_zero<int>(std::max<size_t>(1, P.tiles.size()) * VXH_TILE_XH);
+    B.tile_xhn = D.alloc_zero<int>(std::max<size_t>(1, P.tiles.size()));
+    B.n_tiles = (int)P.tiles.size();
+    B.tiles = D.upload(P.tiles);
+    B.tile_vox = D.upload(P.tile_vox);
+    B.tile_bond = D.upload(P.tile_bond);
+    B.tile_bcls = D.upload(P.tile_bcls);
+    B.tile_bslot = D.upload(P.tile_bslot);
+    B.nx = std::max(P.nx_total, 64);
+    B.xslot = D.upload(P.xslot);
+    B.xplanes = P.any_fluid_tiles ? 28 : 16;
+    B.xch = D.alloc_zero<unsigned long long>(no_tiles ? 1 : (size_t)3 * B.xplanes * B.nx);
+    B.n_tmv = P.n_tmv; B.n_tf = P.n_tf;       // fluid tiles: their parts of the drag mesh
+    B.tile_mvert = D.upload(P.tile_mvert); B.tile_mv0 = D.upload(P.tile_mv0); B.tile_facet = D.upload(P.tile_facet);
+    B.tile_ffirst = D.upload(P.tile_ffirst); B.tile_fcount = D.upload(P.tile_fcount);
+    B.tile_mvox = D.upload(P.tile_mvox);
+    B.tile_mv = D.alloc_zero<unsigned long long>(std::max<size_t>(1, P.tiles.size()) * 3 * VXH_TILE_MV_STRIDE);
+    D.n_rest = P.n_rest; D.n_all = P.n_all;
+    D.streamed_all = D.upload(P.streamed_all);
+    D.streamed_rest = D.upload(P.streamed_rest);
+    D.groups.clear();
+    for (size_t gi = 0; gi < P.groups.size(); ++gi) {
+        D.groups.emplace_back(std::move(P.groups[gi]));
+        Device::Group& g = D.groups.back();
+        g.list = D.upload(g.robots);
+        if (g.order_use) for (int k = 0; k < 2; ++k) g.order_bits[k] = D.alloc_zero<unsigned long long>((size_t)(g.count + 63) / 64 + 1);
+        D.give_stream(g, gi);
     }
-    B.n_tiles = (int)h_tiles.size();
-    B.tiles = D.upload(h_tiles);
-    B.tile_vox = D.upload(tile_vox);
-    B.tile_bond = D.upload(tile_bond);
-    B.tile_bcls = D.upload(tile_bcls);
-    B.tile_bslot = D.upload(tile_bslot);
-    B.nx = std::max(nx_total, 64);
-    B.xslot = D.upload(xslot);
-    B.xplanes = any_fluid_tiles ? 28 : 16;
-    B.xch = D.alloc_zero<unsigned long long>(h_tiles.empty() ? 1 : (size_t)3 * B.xplanes * B.nx);
-    {   // fluid tiles: their parts of the drag mesh
-        const size_t nm = tmv_v0[0].size(), nf = tf_owner.size();
-        std::vector<int> mvert(std::max<size_t>(1, 8 * nm), -1), facet(std::max<size_t>(1, 4 * nf), 0);
-        std::vector<double> mv0(std::max<size_t>(1, 3 * nm), 0.0);
-        for (int c = 0; c < 8; ++c) for (size_t i = 0; i < nm; ++i) mvert[(size_t)c * nm + i] = tmv_slot[c][i];
-        for (int c = 0; c < 3; ++c) for (size_t i = 0; i < nm; ++i) mv0[(size_t)c * nm + i] = tmv_v0[c][i];
-        for (size_t f = 0; f < nf; ++f) { facet[f] = tf_owner[f]; for (int c = 0; c < 3; ++c) facet[(size_t)(c + 1) * nf + f] = tf_vert[c][f]; }
-        tile_ffirst.resize(std::max<size_t>(1, tile_vox.size()), 0); tile_fcount.resize(std::max<size_t>(1, tile_vox.size()), 0);
-        B.n_tmv = (int)nm; B.n_tf = (int)nf;
-        B.tile_mvert = D.upload(mvert); B.tile_mv0 = D.upload(mv0); B.tile_facet = D.upload(facet);
-        B.tile_ffirst = D.upload(tile_ffirst); B.tile_fcount = D.upload(tile_fcount);
-        if (tile_mvox.empty()) tile_mvox.push_back(0);
-        B.tile_mvox = D.upload(tile_mvox);
-    }
-    B.tile_mv = D.alloc_zero<unsigned long long>(std::max<size_t>(1, h_tiles.size()) * 3 * VXH_TILE_MV_STRIDE);
-    {   // fused path: launch groups by kernel variant; inside a group the longest-running robots first
-        D.groups.clear();
-        for (int r = 0; r < nr; ++r) {
-            if (D.robot_tiled[r]) continue;
-            const FusedVariant fv = fused_variant(robots_[r], variant_, opt_);
-            if (fv.block == 0) continue;                              // streaming kernels
-            Device::Group* g = nullptr;
-            for (auto& q : D.groups) if (q.block == fv.block && q.nacc == fv.nacc && q.fluid == fv.fluid && q.tabg == fv.tabg && q.wide == fv.wide && q.two_tiles == fv.two_tiles) g = &q;
-            if (!g) { D.groups.emplace_back(); g = &D.groups.back(); g->block = fv.block; g->nacc = fv.nacc; g->fluid = fv.fluid; g->tabg = fv.tabg; g->wide = fv.wide; g->two_tiles = fv.two_tiles; }
-            g->robots.push_back(r);
-            g->lds = std::max(g->lds, fv.lds);
-        }
-        {
-            // masks of the robots the streaming kernels step: everything the other kernels do not take / (option fused = 0)
-            // everything but the tiled robots
-            std::vector<unsigned char> all(std::max(nr, 1), 1), rest(std::max(nr, 1), 1);
-            for (auto& g : D.groups) for (int r : g.robots) rest[r] = 0;
-            for (int r = 0; r < nr; ++r) if (D.robot_tiled[r]) all[r] = rest[r] = 0;
-            D.n_rest = D.n_all = 0;
-            for (int r = 0; r < nr; ++r) { if (rest[r] && robots_[r].nvox > 0) ++D.n_rest; if (all[r] && robots_[r].nvox > 0) ++D.n_all; }
-            D.streamed_all = D.upload(all);
-            D.streamed_rest = D.upload(rest);
-        }
-        size_t gi = 0;
-        for (auto& g : D.groups) {
-            std::stable_sort(g.robots.begin(), g.robots.end(), [&](int a, int b) {
-                return (double)robots_[a].planned_steps * robots_[a].nvox > (double)robots_[b].planned_steps * robots_[b].nvox; });
-            g.count = (int)g.robots.size();
-            g.list = D.upload(g.robots);
-            g.order_valid = false; g.order_cur = 0; g.order_use = false;
-            if (!g.wide) {                  // (k_robot_steps; colliding robots only: the others have no broad-phase runs to spread)
-                for (int r : g.robots) if (robots_[r].vxa.self_col_enabled) g.order_use = true;
-                if (g.order_use) for (int k = 0; k < 2; ++k) g.order_bits[k] = D.alloc_zero<unsigned long long>((size_t)(g.count + 63) / 64 + 1);
-            }
-            if (D.group_streams.size() <= gi) {
-                hipStream_t st; hipEvent_t e0, e1;
-                // launch groups of one call are meant to run side by side (two size classes of one population: 64 + 64 workgroups on 256
-                // CUs).  Streams share a few hardware queues, handed out round robin as streams are created: two group streams that
-                // land on the same queue run their kernels one after the other (measured: the same 64 robots of two size classes
-                // 14.8 or 24.3 us per step, depending on how many streams the process had created before).  Streams of different
-                // priority never share a queue, so the group streams cycle through the priorities the device offers.
-                int least = 0, greatest = 0;
-                HIP_OK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-                const int span = least - greatest + 1;                 // (numerically: greatest priority = smallest number)
-                const int prio = span > 1 ? greatest + (int)(D.group_streams.size() % (size_t)span) : 0;
-                HIP_OK(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, prio));
-                HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1));
-                D.group_streams.push_back(st); D.group_events.push_back(e0); D.group_events.push_back(e1);
-            }
-            g.stream = D.group_streams[gi]; g.t0 = D.group_events[2 * gi]; g.t1 = D.group_events[2 * gi + 1];
-            ++gi;
-        }
-    }
-    {   // streaming path: one rebuild block per 256 surface voxels of every colliding robot
-        std::vector<int> rr, ri;
-        for (int r = 0; r < nr; ++r)
-            if (robots_[r].vxa.self_col_enabled)
-                for (int i0 = 0; i0 < robots_[r].nsurf; i0 += 256) { rr.push_back(r); ri.push_back(i0); }
-        D.reb_blocks = (int)rr.size();
-        D.reb_robot = D.upload(rr);
-        D.reb_i0 = D.upload(ri);
-    }
+    D.reb_blocks = (int)P.reb_robot.size();
+    D.reb_robot = D.upload(P.reb_robot);
+    D.reb_i0 = D.upload(P.reb_i0);
 #ifdef VXH_PHASE_TIMING
     B.prof = D.alloc_zero<unsigned long long>(16 * 8 + 256 * 8);
 #endif
     B.small_angle_w = std::cos(VXH_SMALL_ANGLE_RAD * 0.5);                    // Vec3D.h:55-59
     B.smallish_angle_w = std::cos(VXH_HYST * VXH_SMALL_ANGLE_RAD * 0.5);
     B.slthresh_acos2sqrt = 1.0 - 0.9988 * 0.9988;
-    HIP_OK(hipStreamSynchronize(D.stream));      // every upload has left the host vectors above
+    HIP_OK(hipStreamSynchronize(D.stream));      // every upload has left the host tables
     D.verify_uploads("at the end of prepare()");
+    // what outlives the call: the rest of the host tables (hundreds of megabytes for a large population) ends here
+    D.h_robot = std::move(H.robot);
+    D.vox_begin = std::move(H.vox_begin); D.surf_begin = std::move(H.surf_begin); D.total_surf = ns;
+    D.trace_begin = std::move(H.trace_begin); D.trace_cap = std::move(H.trace_cap); D.total_trace = H.total_trace;
+    D.max_planned = H.max_planned; D.max_nvox = H.max_nvox;
+    D.robot_tiled = std::move(P.robot_tiled); D.robot_tiles = std::move(P.robot_tiles);
     hs.mark("kernel choice, tiling, launch groups");
     hs.print("prepare");
     prepared_ = true;
@@ -1400,6 +776,7 @@ void Engine::prepare()
 
 void Engine::reset() { if (!robots_.empty()) prepare(); }
 
+// (which kernel variant takes a robot -- fused_variant, wide_listed, resident_block -- is decided in batch.cpp; a Group carries the answer)
 static void launch_group(const DBatch& B, int block, bool fluid, bool tabg, bool wide, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters, int two_tiles = 0,
                          const unsigned long long* order_in = nullptr, unsigned long long* order_out = nullptr)
 {

@@ -36,7 +36,7 @@ struct Options {
     int tiled = 1;                             // several workgroups per robot (kernels_tiled.hpp): 0 never, 1 when the population is too
                                                // small to fill the CUs one robot each or a robot has more than 1024 voxels, 2 always
     int tiles_per_robot = 0;                   // 0 = chosen from the population size; > 0: requested for every tiled robot (tests)
-    int tile_small = 0;                        // also tile large robots the resident kernel could take when the population is small (see prepare())
+    int tile_small = 0;                        // also tile large robots the resident kernel could take when the population is small (see tile_candidates(), batch.cpp)
     int wide = 1;                              // small robots (up to 512 voxels, 1023 bonds) go to the wide kernel (kernels_wide.hpp); 0: resident kernel
     int wide_two_tiles = 1;                    // ... with a second pose tile in LDS where it fits (two barriers per step instead of three); 0: cross-checks
     int col_cap = 0;                           // partners a contact row can hold; 0 = every other surface voxel (unbounded, like the reference)

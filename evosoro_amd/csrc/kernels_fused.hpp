@@ -32,7 +32,7 @@
 
 namespace vxh {
 
-enum { VXH_FUSED_STATIC_LDS = 480 };      // upper bound of the kernel's static __shared__ variables
+// (VXH_FUSED_STATIC_LDS, the upper bound of the kernel's static __shared__ variables: device_types.hpp, the host sizes the launch with it)
 
 // developer instrumentation (scripts/dev_gpu_diag.py phases; library built with -DVXH_PHASE_TIMING): per-wave cycle sums
 // of the phases of a step

@@ -1,8 +1,8 @@
 // Batch assembly and launch planning (batch.hpp): everything Engine::prepare() works out on the host before it uploads.
 #include "batch.hpp"
+#include "import.hpp"      // for_each_index
 
 #include <algorithm>
-#include <atomic>
 #include <cfloat>
 #include <cmath>
 #include <cstdio>
@@ -10,7 +10,6 @@
 #include <cstring>
 #include <stdexcept>
 #include <string>
-#include <thread>
 
 namespace vxh {
 
@@ -451,13 +450,7 @@ HostBatch assemble_batch(const std::vector<RobotModel>& robots, int variant, con
     lay_out_tables(robots, variant, opt, device_mem, H);
     // the robots are assembled on the host cores (disjoint ranges)
     const int nr = (int)robots.size();
-    std::atomic<int> next{0};
-    auto worker = [&]() { for (int r = next.fetch_add(1); r < nr; r = next.fetch_add(1)) assemble_robot(robots[r], r, variant, opt, H); };
-    const int nthreads = std::max(1, std::min({nr / 8, (int)std::thread::hardware_concurrency(), 32}));
-    std::vector<std::thread> pool;
-    for (int t = 1; t < nthreads; ++t) pool.emplace_back(worker);
-    worker();
-    for (auto& t : pool) t.join();
+    for_each_index(nr, std::min(nr / 8, 32), [&](int r) { assemble_robot(robots[r], r, variant, opt, H); });
     return H;
 }
 
@@ -757,6 +750,45 @@ LaunchPlan plan_launches(const std::vector<RobotModel>& robots, const HostBatch&
         if (robots[r].vxa.self_col_enabled)
             for (int i0 = 0; i0 < robots[r].nsurf; i0 += 256) { P.reb_robot.push_back(r); P.reb_i0.push_back(i0); }
     return P;
+}
+
+// ---- dominant_kernel: which unit of a call did most of its work ----
+DominantKernel dominant_kernel(const std::vector<RobotModel>& robots, const std::vector<int>& steps, const std::vector<const GroupPlan*>& groups,
+                               const std::vector<unsigned char>& robot_tiled, bool fused, bool tiled, bool streaming, int n_rest, long long todo,
+                               const std::vector<long long>& group_launches, long long tile_launch_count)
+{
+    struct Work { double vs = 0, ab = 0; };      // voxel-steps, algorithmic bytes
+    auto add = [&](Work& w, int r) {
+        const double ds = steps[r];
+        w.vs += ds * robots[r].nvox; w.ab += ds * (224.0 * robots[r].nvox + 144.0 * robots[r].nbond);
+    };
+    Work all, tiles;
+    int n_tiled = 0;
+    for (size_t r = 0; r < robots.size(); ++r) {
+        if (robots[r].nvox) add(all, (int)r);
+        if (robot_tiled[r]) { add(tiles, (int)r); ++n_tiled; }
+    }
+    std::vector<Work> grp(fused ? groups.size() : 0);
+    size_t best = 0;
+    double grp_best = 0;
+    for (size_t k = 0; k < grp.size(); ++k) {
+        for (int r : groups[k]->robots) add(grp[k], r);
+        if (grp[k].vs > grp[best].vs) best = k;
+        grp_best = std::max(grp_best, grp[k].vs);
+    }
+    // The rule, and it is not symmetric.  The tiles win when they did at least as much (>=) as the best group AND as everything else
+    // without that group: all - tiles - best group, i.e. the streamed rest TOGETHER WITH every other group -- so they can lose although
+    // they beat every single unit.  The best group (the first of equals) is then compared with the streamed rest alone, all - tiles -
+    // EVERY group, and keeps the call unless the rest did strictly more (>).  Without launch groups: whatever was not tiled.
+    typedef DominantKernel D;
+    auto unit = [](D::Unit u, int group, int block, int n, long long launches, const Work& w) { return D{u, group, block, n, launches, w.ab, w.vs}; };
+    if (tiled && tiles.vs >= grp_best && tiles.vs >= all.vs - tiles.vs - grp_best) return unit(D::TILES, -1, 1, n_tiled, tile_launch_count, tiles);
+    Work rest = {all.vs - tiles.vs, all.ab - tiles.ab};
+    if (grp.empty()) return unit(D::STREAMED, -1, 0, (int)robots.size() - n_tiled, todo, rest);
+    for (const Work& g : grp) { rest.vs -= g.vs; rest.ab -= g.ab; }
+    if (streaming && rest.vs > grp[best].vs) return unit(D::REST, -1, 0, n_rest, todo, rest);
+    const GroupPlan& g = *groups[best];
+    return unit(D::GROUP, (int)best, g.block + (g.wide ? 1 : 0), g.count, group_launches[best], grp[best]);
 }
 
 }  // namespace vxh

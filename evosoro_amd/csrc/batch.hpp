@@ -108,4 +108,18 @@ struct LaunchPlan {
 };
 LaunchPlan plan_launches(const std::vector<RobotModel>& robots, const HostBatch& H, int variant, const Options& opt, bool tiling_allowed, int n_cu);
 
+// The dominant kernel of one call (vxh_counters::dominant_*): the unit -- the tiled launches, one launch group, the streaming kernels
+// next to the groups (REST), or the streaming kernels alone (STREAMED: a call without launch groups) -- that processed most voxel-steps.
+struct DominantKernel {
+    enum Unit { TILES, GROUP, REST, STREAMED } unit = STREAMED;
+    int group = -1;                   // GROUP: which
+    int block = 0, robots = 0;        // block: 1 = k_tile_steps, 0 = the streaming kernels; a group: its workgroup size, + 1 for the wide kernel
+    long long launches = 0;
+    double alg_bytes = 0, voxel_steps = 0;
+};
+// steps: what each robot took in this call; fused, tiled, streaming: the paths the call used; todo: its step rounds
+DominantKernel dominant_kernel(const std::vector<RobotModel>& robots, const std::vector<int>& steps, const std::vector<const GroupPlan*>& groups,
+                               const std::vector<unsigned char>& robot_tiled, bool fused, bool tiled, bool streaming, int n_rest, long long todo,
+                               const std::vector<long long>& group_launches, long long tile_launch_count);
+
 }  // namespace vxh

@@ -1,17 +1,24 @@
-// Host-only check of batch assembly and launch planning (batch.hpp): no HIP, built with the plain C++ compiler (make batch_check), so it
-// also runs under the host sanitizers.  usage: batch_check <variant 0|1> <CUs> robot.vxa...   All robots form ONE batch, assembled and
-// planned under several option sets; every table is then unpacked and compared with the robots' models.  Exit status 0 = all consistent.
+// Host-only check of the import pipeline (import.hpp), batch assembly, launch planning and the dominant-kernel choice (batch.hpp): no HIP,
+// built with the plain C++ compiler (make batch_check), so it also runs under the host sanitizers.  Exit status 0 = all consistent.
+//   batch_check <variant 0|1> <CUs> robot.vxa...    all robots form ONE batch, assembled and planned under several option sets; every table
+//                                                  is then unpacked and compared with the robots' models
+//   batch_check --arrays <variant 0|1> robot.vxa... every file's lattice and layers handed over as arrays (models_from_arrays) must give the
+//                                                  batch the file gives, value for value; and what that route must refuse
+//   batch_check --dominant                         dominant_kernel on a table of hand-made calls, one per branch of its rule
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <fstream>
 #include <map>
 #include <sstream>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "batch.hpp"
+#include "import.hpp"
 
 using namespace vxh;
 
@@ -239,24 +246,205 @@ void check_batch(const Robots& robots, int variant, int n_cu, const char* name, 
                 name, nr, H.nv, P.groups.size(), P.tile_launches.size(), n_tiled, P.tiles.size(), P.n_rest);
 }
 
+// ---- --arrays: the in-memory route (models_from_arrays, what vxh_add_robots takes) against the file route ----
+struct FileLayer { const char* tag; bool VxaModel::*has; std::vector<double> VxaModel::*values; };
+const FileLayer file_layers[] = {
+    {"PhaseOffset", &VxaModel::has_phase_offset, &VxaModel::phase_offset}, {"TempAmpDamp", &VxaModel::has_temp_amp_damp, &VxaModel::temp_amp_damp},
+    {"Stiffness", &VxaModel::has_stiffness, &VxaModel::stiffness}, {"FinalPhaseOffset", &VxaModel::has_final_phase_offset, &VxaModel::final_phase_offset},
+    {"FinalTempAmpDamp", &VxaModel::has_final_temp_amp_damp, &VxaModel::final_temp_amp_damp}, {"InitialVoxelSize", &VxaModel::has_initial_voxel_size, &VxaModel::initial_voxel_size},
+    {"FinalVoxelSize", &VxaModel::has_final_voxel_size, &VxaModel::final_voxel_size}, {"GrowthTime", &VxaModel::has_growth_time, &VxaModel::growth_time},
+    {"StartGrowthTime", &VxaModel::has_start_growth_time, &VxaModel::start_growth_time},
+};
+
+// a file's own lattice and layers handed back as arrays: material = structure, every present layer expanded from per-occupied-voxel values to the full lattice
+struct ArraysOfFile {
+    std::vector<std::vector<double>> full;
+    std::vector<const char*> tags;
+    std::vector<const double*> ptrs;
+    vxh_robot_arrays A{};
+    explicit ArraysOfFile(const VxaModel& vxa)
+    {
+        for (const FileLayer& l : file_layers) {
+            if (!(vxa.*(l.has))) continue;
+            std::vector<double> f(vxa.structure.size(), 0.0);
+            size_t occupied = 0;
+            for (size_t k = 0; k < f.size(); ++k) if (vxa.structure[k]) f[k] = (vxa.*(l.values)).at(occupied++);
+            full.push_back(std::move(f)); tags.push_back(l.tag);
+        }
+        for (const auto& f : full) ptrs.push_back(f.data());
+        A.nx = vxa.nx; A.ny = vxa.ny; A.nz = vxa.nz; A.material = vxa.structure.data();
+        A.n_layers = (int)full.size(); A.layer_tags = tags.data(); A.layers = ptrs.data();
+    }
+    ArraysOfFile(const ArraysOfFile&) = delete;
+};
+
+template <class T>
+void same_values(const char* what, const std::vector<T>& a, const std::vector<T>& b)
+{
+    static_assert(std::is_arithmetic<T>::value, "element-wise comparison of numbers");
+    CHECK(a.size() == b.size(), "%s: %zu against %zu elements", what, a.size(), b.size());
+    for (size_t i = 0; i < a.size(); ++i) CHECK(a[i] == b[i], "%s[%zu] differs", what, i);
+}
+// (bytewise: only for structs without padding)
+static_assert(sizeof(DVoxClass) == 12 * sizeof(double) + 2 * sizeof(int), "DVoxClass has padding");
+static_assert(sizeof(DBondClass) == 20 * sizeof(double) + 2 * sizeof(int), "DBondClass has padding");
+static_assert(sizeof(DRobot) == 24 * sizeof(int) + 2 * sizeof(long long) + 17 * sizeof(double) + 2 * sizeof(float), "DRobot has padding");
+static_assert(sizeof(DRobotState) == 11 * sizeof(double) + sizeof(unsigned long long) + 12 * sizeof(int), "DRobotState has padding");
+template <class T>
+void same_bytes(const char* what, const std::vector<T>& a, const std::vector<T>& b)
+{
+    CHECK(a.size() == b.size(), "%s: %zu against %zu elements", what, a.size(), b.size());
+    for (size_t i = 0; i < a.size(); ++i) CHECK(std::memcmp(&a[i], &b[i], sizeof(T)) == 0, "%s[%zu] differs", what, i);
+}
+
+void same_batch(const HostBatch& a, const HostBatch& b)
+{
+#define SCALAR(f) CHECK(a.f == b.f, #f " differs")
+#define VALUES(f) same_values(#f, a.f, b.f)
+#define BYTES(f) same_bytes(#f, a.f, b.f)
+    SCALAR(nv); SCALAR(ns); SCALAR(total_trace); SCALAR(max_planned); SCALAR(max_nvox); SCALAR(any_dev); SCALAR(any_mesh); SCALAR(any_fluid);
+    SCALAR(total_mv); SCALAR(total_facet); SCALAR(col_total);
+    BYTES(robot); BYTES(rstate); BYTES(vtab); BYTES(btab);
+    VALUES(vox_begin); VALUES(surf_begin); VALUES(trace_begin); VALUES(trace_cap); VALUES(wave_robot); VALUES(nbr); VALUES(surf); VALUES(surf_code);
+    VALUES(surf_ord); VALUES(excl); VALUES(vclass); VALUES(bclass); VALUES(sched_off); VALUES(bsched); VALUES(wl_off); VALUES(wlist); VALUES(wgather);
+    VALUES(amp_damp); VALUES(dev); VALUES(act_sb); VALUES(act_cb); VALUES(px); VALUES(py); VALUES(pz); VALUES(sc); VALUES(qw); VALUES(small);
+    VALUES(mv_begin); VALUES(facet_begin); VALUES(vert_pack); VALUES(vert_vox); VALUES(vert_robot); VALUES(vert_v0); VALUES(facet_vox); VALUES(facet_vert);
+    VALUES(facet_first); VALUES(facet_robot); VALUES(facet_count); VALUES(vtab_off); VALUES(btab_off); VALUES(excl_off); VALUES(col_off); VALUES(col_cap);
+    VALUES(img_idx);
+#undef SCALAR
+#undef VALUES
+#undef BYTES
+}
+
+void expect_refusal(const char* what, const std::string& text, const vxh_robot_arrays* in, int n, int variant, const char* message)
+{
+    g_set = what;
+    try {
+        models_from_arrays(text.data(), text.size(), in, n, false, variant, false);
+    } catch (const std::invalid_argument& ex) {
+        CHECK(std::strstr(ex.what(), message), "refused with \"%s\", expected \"%s\"", ex.what(), message);
+        return;
+    }
+    fail("accepted, expected the refusal \"%s\"", message);
+}
+
+// what models_from_arrays must refuse, on variations of one good robot
+void check_refusals(const std::string& text, const vxh_robot_arrays& good, int variant)
+{
+    const size_t cells = (size_t)good.nx * good.ny * good.nz;
+    vxh_robot_arrays A = good;
+    A.nx = 0; expect_refusal("nx = 0", text, &A, 1, variant, "bad lattice");
+    A = good; A.material = nullptr; expect_refusal("no material", text, &A, 1, variant, "bad lattice");
+    const std::vector<unsigned char> wrong(cells, 200);
+    A = good; A.material = wrong.data(); expect_refusal("material 200", text, &A, 1, variant, "material index outside the palette");
+    const std::vector<double> layer(cells, 0.5);
+    const char* tag = "Bogus"; const double* values = layer.data();
+    A = good; A.n_layers = 1; A.layer_tags = &tag; A.layers = &values;
+    expect_refusal("unknown layer", text, &A, 1, variant, "unsupported per-voxel layer <Bogus>");
+    tag = "GrowthTime";
+    if (variant == 1) expect_refusal("land-only layer", text, &A, 1, variant, "unsupported <GrowthTime> development layer (land_water)");
+    A.layer_tags = nullptr; expect_refusal("no tag array", text, &A, 1, variant, "bad layer arrays");
+    A.layer_tags = &tag; A.layers = nullptr; expect_refusal("no layer array", text, &A, 1, variant, "bad layer arrays");
+    A.n_layers = -1; expect_refusal("n_layers = -1", text, &A, 1, variant, "bad layer arrays");
+    A.n_layers = 1; A.layers = &values; tag = nullptr; expect_refusal("null tag", text, &A, 1, variant, "null layer tag or layer");
+    tag = "PhaseOffset"; values = nullptr; expect_refusal("null layer", text, &A, 1, variant, "null layer tag or layer");
+    // of several bad robots the first IN INDEX ORDER is reported, whichever thread met which
+    std::vector<vxh_robot_arrays> many(40, good);
+    many[17].material = wrong.data(); many[30].nx = 0;
+    expect_refusal("40 robots, 17 and 30 bad", text, many.data(), 40, variant, "material index outside the palette");
+}
+
+void check_arrays(int variant, const std::vector<std::string>& paths)
+{
+    const Robots by_file = build_vxa_files(paths, variant, false);
+    for (size_t i = 0; i < paths.size(); ++i) {
+        g_set = paths[i].c_str();
+        std::ifstream in(paths[i], std::ios::binary);
+        std::stringstream ss;
+        ss << in.rdbuf();
+        const std::string text = ss.str();
+        const VxaModel vxa = read_vxa(text.data(), text.size(), variant);
+        const ArraysOfFile arrays(vxa);
+        const Robots by_arrays = build_models(models_from_arrays(text.data(), text.size(), &arrays.A, 1, false, variant, false));
+        CHECK(by_arrays.size() == 1 && by_arrays[0].nvox == by_file[i].nvox && by_arrays[0].nbond == by_file[i].nbond, "the robot built from arrays has other dimensions");
+        same_batch(assemble_batch(by_arrays, variant, Options(), 0), assemble_batch(Robots(1, by_file[i]), variant, Options(), 0));
+        if (i == 0) check_refusals(text, arrays.A, variant);
+        std::printf("batch_check --arrays [%s]: %d voxels, %d layers: the same batch as from the file: ok\n", paths[i].c_str(), by_file[i].nvox, arrays.A.n_layers);
+    }
+}
+
+// ---- --dominant: dominant_kernel on hand-made calls; the expected values were worked out from the rule by hand ----
+struct DomRobot { int nvox, nbond, steps, tiled; };
+struct DomCase {
+    const char* name;
+    std::vector<DomRobot> robots;
+    std::vector<std::vector<int>> groups;      // group k: block 256 * (k + 1), wide when k is odd
+    bool fused, tiled, streaming;
+    int n_rest; long long todo; std::vector<long long> group_launches; long long tile_launch_count;
+    DominantKernel want;                       // {unit, group, block, robots, launches, alg_bytes, voxel_steps}
+};
+
+void check_dominant()
+{
+    typedef DominantKernel D;
+    const std::vector<DomCase> cases = {
+        // all 21500, tiles 20000, group 1000, rest 500
+        {"the tiles win", {{2000, 5000, 10, 1}, {100, 200, 10, 0}, {50, 80, 10, 0}}, {{1}}, true, true, true, 1, 10, {1}, 2,
+         {D::TILES, -1, 1, 1, 2, 10 * (224.0 * 2000 + 144.0 * 5000), 20000}},
+        {"the tiles tie with the best group: the tiles, by >=", {{100, 150, 10, 1}, {100, 0, 10, 0}}, {{1}}, true, true, false, 0, 10, {1}, 3,
+         {D::TILES, -1, 1, 1, 3, 10 * (224.0 * 100 + 144.0 * 150), 1000}},
+        // groups 1500 and 2000 (a robot that took 5 steps while the others took 10)
+        {"the best of two groups", {{100, 0, 10, 0}, {400, 30, 5, 0}, {50, 0, 10, 0}}, {{0, 2}, {1}}, true, false, false, 0, 10, {4, 7}, 0,
+         {D::GROUP, 1, 513, 1, 7, 5 * (224.0 * 400 + 144.0 * 30), 2000}},
+        {"two groups tie: the first", {{100, 10, 10, 0}, {100, 0, 10, 0}}, {{0}, {1}}, true, false, false, 0, 10, {4, 7}, 0,
+         {D::GROUP, 0, 256, 1, 4, 10 * (224.0 * 100 + 144.0 * 10), 1000}},
+        {"the streamed rest beats the best group", {{100, 0, 10, 0}, {300, 20, 10, 0}}, {{0}}, true, false, true, 1, 10, {1}, 0,
+         {D::REST, -1, 0, 1, 10, 10 * (224.0 * 300 + 144.0 * 20), 3000}},
+        {"the rest ties with the best group: the group, by >", {{100, 0, 10, 0}, {100, 0, 10, 0}}, {{0}}, true, false, true, 1, 10, {5}, 0,
+         {D::GROUP, 0, 256, 1, 5, 10 * 224.0 * 100, 1000}},
+        // the option fused = 0: the plan still has its group, the call did not use it; the small tiled robot (500 of 3500) does not win
+        {"fused = 0: everything streamed", {{100, 0, 10, 0}, {200, 10, 10, 0}, {50, 0, 10, 1}}, {{0, 1}}, false, true, true, 0, 10, {0}, 1,
+         {D::STREAMED, -1, 0, 2, 10, 10 * (224.0 * 300 + 144.0 * 10), 3000}},
+        // tiles 1000 against groups of 900, 800 and 700: more than every single unit, less than all - tiles - best group = 1500
+        {"the other groups together outweigh the tiles", {{100, 0, 10, 1}, {90, 0, 10, 0}, {80, 0, 10, 0}, {70, 0, 10, 0}}, {{1}, {2}, {3}}, true, true, false, 0, 10, {2, 2, 2}, 1,
+         {D::GROUP, 0, 256, 1, 2, 10 * 224.0 * 90, 900}},
+    };
+    for (const DomCase& c : cases) {
+        g_set = c.name;
+        Robots robots(c.robots.size());
+        std::vector<int> steps;
+        std::vector<unsigned char> robot_tiled;
+        for (size_t r = 0; r < c.robots.size(); ++r) {
+            robots[r].nvox = c.robots[r].nvox; robots[r].nbond = c.robots[r].nbond;
+            steps.push_back(c.robots[r].steps); robot_tiled.push_back((unsigned char)c.robots[r].tiled);
+        }
+        std::vector<GroupPlan> plans(c.groups.size());
+        std::vector<const GroupPlan*> groups;
+        for (size_t k = 0; k < plans.size(); ++k) {
+            plans[k].block = 256 * ((int)k + 1); plans[k].wide = (int)(k & 1); plans[k].robots = c.groups[k]; plans[k].count = (int)c.groups[k].size();
+            groups.push_back(&plans[k]);
+        }
+        const D got = dominant_kernel(robots, steps, groups, robot_tiled, c.fused, c.tiled, c.streaming, c.n_rest, c.todo, c.group_launches, c.tile_launch_count);
+        CHECK(got.unit == c.want.unit && got.group == c.want.group, "unit %d group %d, expected unit %d group %d", (int)got.unit, got.group, (int)c.want.unit, c.want.group);
+        CHECK(got.block == c.want.block && got.robots == c.want.robots && got.launches == c.want.launches, "block %d, %d robots, %lld launches; expected %d, %d, %lld",
+              got.block, got.robots, got.launches, c.want.block, c.want.robots, c.want.launches);
+        CHECK(got.alg_bytes == c.want.alg_bytes && got.voxel_steps == c.want.voxel_steps, "%.17g bytes, %.17g voxel-steps; expected %.17g, %.17g",
+              got.alg_bytes, got.voxel_steps, c.want.alg_bytes, c.want.voxel_steps);
+        std::printf("batch_check --dominant [%s]: ok\n", c.name);
+    }
+}
+
 }  // namespace
 
 int main(int argc, char** argv)
 {
-    if (argc < 4) { std::fprintf(stderr, "usage: batch_check <variant 0|1> <CUs> robot.vxa...\n"); return 2; }
-    const int variant = std::atoi(argv[1]), n_cu = std::atoi(argv[2]);
-    Robots robots;
+    const std::string mode = argc > 1 ? argv[1] : "";
     try {
-        for (int i = 3; i < argc; ++i) {
-            std::ifstream in(argv[i], std::ios::binary);
-            if (!in) throw std::runtime_error(std::string("io: cannot open ") + argv[i]);
-            std::stringstream ss;
-            ss << in.rdbuf();
-            const std::string text = ss.str();
-            const VxaModel vxa = read_vxa(text.data(), text.size(), variant);
-            if (!vxa.unsupported.empty()) throw std::runtime_error(std::string(argv[i]) + ": unsupported " + vxa.unsupported.front());
-            robots.push_back(build_robot(vxa));
-        }
+        if (mode == "--dominant") { check_dominant(); return 0; }
+        if (mode == "--arrays" && argc >= 4) { check_arrays(std::atoi(argv[2]), std::vector<std::string>(argv + 3, argv + argc)); return 0; }
+        if (argc < 4 || mode[0] == '-') { std::fprintf(stderr, "usage: batch_check <variant 0|1> <CUs> robot.vxa... | --arrays <variant 0|1> robot.vxa... | --dominant\n"); return 2; }
+        const int variant = std::atoi(argv[1]), n_cu = std::atoi(argv[2]);
+        const Robots robots = build_vxa_files(std::vector<std::string>(argv + 3, argv + argc), variant, false);
         Options o;
         check_batch(robots, variant, n_cu, "defaults", o);
         o = Options(); o.wide = 0;

@@ -43,6 +43,25 @@ int guarded(vxh_engine* e, F&& body)
 
 bool bad_robot(const vxh_engine* e, int robot) { return !e || !e->impl || robot < 0 || robot >= e->impl->num_robots(); }
 
+// The frame of the entry points that look at one .vxa without an engine: read, refuse, build, then body(model), which returns null or why
+// the caller's arguments do not fit the model (VXH_ERR_ARG).  What went wrong goes into errbuf; of the unsupported features, the first.
+template <class F>
+int inspected(const char* xml, size_t len, int variant, char* errbuf, size_t errcap, F&& body)
+{
+    auto fail = [&](int code, const char* what) {
+        if (errbuf && errcap) { std::strncpy(errbuf, what, errcap - 1); errbuf[errcap - 1] = 0; }
+        return code;
+    };
+    try {
+        const vxh::VxaModel vxa = vxh::read_vxa(xml, len, variant);
+        if (!vxa.unsupported.empty()) return fail(VXH_ERR_UNSUPPORTED, vxa.unsupported.front().c_str());
+        const char* misfit = body(vxh::build_robot(vxa));
+        return misfit ? fail(VXH_ERR_ARG, misfit) : VXH_OK;
+    } catch (const std::exception& ex) {
+        return fail(VXH_ERR_PARSE, ex.what());
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -50,65 +69,40 @@ extern "C" {
 int vxh_inspect_vxa_buffer(const char* xml, size_t len, int variant, vxh_model_info* out, char* errbuf, size_t errcap)
 {
     if (!xml || !out || (variant != VXH_VOXCAD && variant != VXH_VOXCAD_LAND_WATER)) return VXH_ERR_ARG;
-    auto fail = [&](int code, const char* what) {
-        if (errbuf && errcap) { std::strncpy(errbuf, what, errcap - 1); errbuf[errcap - 1] = 0; }
-        return code;
-    };
-    try {
-        vxh::VxaModel vxa = vxh::read_vxa(xml, len, variant);
-        if (!vxa.unsupported.empty()) return fail(VXH_ERR_UNSUPPORTED, vxa.unsupported.front().c_str());
-        vxh::RobotModel m = vxh::build_robot(vxa);
+    return inspected(xml, len, variant, errbuf, errcap, [&](const vxh::RobotModel& m) -> const char* {
         std::memset(out, 0, sizeof(*out));
         out->nvox = m.nvox; out->nbond = m.nbond; out->nsurf = m.nsurf;
         out->n_vox_classes = (int)m.vox_classes.size(); out->n_bond_classes = (int)m.bond_classes.size();
         out->opt_dt = m.opt_dt; out->dt = m.dt; out->planned_steps = m.planned_steps;
         out->alg_bytes_per_step = 224.0 * m.nvox + 144.0 * m.nbond;
-        return VXH_OK;
-    } catch (const std::exception& ex) {
-        return fail(VXH_ERR_PARSE, ex.what());
-    }
+        return nullptr;
+    });
 }
 
 int vxh_plan_tiles_buffer(const char* xml, size_t len, int variant, int k_request, vxh_tiling_info* out, int* tile_of_out, int capacity,
                           char* errbuf, size_t errcap)
 {
     if (!xml || !out || k_request < 1 || (variant != VXH_VOXCAD && variant != VXH_VOXCAD_LAND_WATER)) return VXH_ERR_ARG;
-    auto fail = [&](int code, const char* what) {
-        if (errbuf && errcap) { std::strncpy(errbuf, what, errcap - 1); errbuf[errcap - 1] = 0; }
-        return code;
-    };
-    try {
-        vxh::VxaModel vxa = vxh::read_vxa(xml, len, variant);
-        if (!vxa.unsupported.empty()) return fail(VXH_ERR_UNSUPPORTED, vxa.unsupported.front().c_str());
-        const vxh::RobotModel m = vxh::build_robot(vxa);
+    return inspected(xml, len, variant, errbuf, errcap, [&](const vxh::RobotModel& m) -> const char* {
         const vxh::TilePlan plan = vxh::plan_tiles(m, k_request);
         std::memset(out, 0, sizeof(*out));
         out->k = plan.k; out->kx = plan.kx; out->ky = plan.ky; out->kz = plan.kz;
         out->max_own = plan.max_own; out->max_local = plan.max_local; out->max_bonds = plan.max_bonds;
         for (const auto& t : plan.tiles) out->total_bonds += (int)t.bond_v1.size();
         if (tile_of_out) {
-            if (capacity < m.nvox) return fail(VXH_ERR_ARG, "tile_of buffer too small");
+            if (capacity < m.nvox) return "tile_of buffer too small";
             for (int v = 0; v < m.nvox; ++v) tile_of_out[v] = plan.tile_of[v];
         }
-        return VXH_OK;
-    } catch (const std::exception& ex) {
-        return fail(VXH_ERR_PARSE, ex.what());
-    }
+        return nullptr;
+    });
 }
 
 int vxh_inspect_constants(const char* xml, size_t len, int variant, double* vox12n, int vox_capacity, double* bond23n, int bond_capacity,
                           char* errbuf, size_t errcap)
 {
     if (!xml || !vox12n || !bond23n || (variant != VXH_VOXCAD && variant != VXH_VOXCAD_LAND_WATER)) return VXH_ERR_ARG;
-    auto fail = [&](int code, const char* what) {
-        if (errbuf && errcap) { std::strncpy(errbuf, what, errcap - 1); errbuf[errcap - 1] = 0; }
-        return code;
-    };
-    try {
-        vxh::VxaModel vxa = vxh::read_vxa(xml, len, variant);
-        if (!vxa.unsupported.empty()) return fail(VXH_ERR_UNSUPPORTED, vxa.unsupported.front().c_str());
-        const vxh::RobotModel m = vxh::build_robot(vxa);
-        if (vox_capacity < m.nvox || bond_capacity < m.nbond) return fail(VXH_ERR_ARG, "constant buffers too small");
+    return inspected(xml, len, variant, errbuf, errcap, [&](const vxh::RobotModel& m) -> const char* {
+        if (vox_capacity < m.nvox || bond_capacity < m.nbond) return "constant buffers too small";
         for (int v = 0; v < m.nvox; ++v) {
             const vxh::VoxClass& c = m.vox_classes[m.vox_class[v]];
             double* o = vox12n + (size_t)12 * v;
@@ -127,10 +121,8 @@ int vxh_inspect_constants(const char* xml, size_t len, int variant, double* vox1
                 o[13] = b.sq_a1m1; o[14] = b.sq_a1m2; o[15] = b.sq_a2i1; o[16] = b.sq_a2i2;
                 o[17] = b.sq_b1m1; o[18] = b.sq_b1m2; o[19] = b.sq_b2fm1; o[20] = b.sq_b2fm2; o[21] = b.sq_b3i1; o[22] = b.sq_b3i2;
             }
-        return VXH_OK;
-    } catch (const std::exception& ex) {
-        return fail(VXH_ERR_PARSE, ex.what());
-    }
+        return nullptr;
+    });
 }
 
 double vxh_convex_hull_volume(const double* xyz, int n)
@@ -336,22 +328,13 @@ int vxh_get_shape_descriptors(const vxh_engine* ce, int robot, int at_end, doubl
 int vxh_inspect_angle_excess(const char* xml, size_t len, int variant, double* out, int capacity, int* count_out, char* errbuf, size_t errcap)
 {
     if (!xml || !count_out || (capacity > 0 && !out) || (variant != VXH_VOXCAD && variant != VXH_VOXCAD_LAND_WATER)) return VXH_ERR_ARG;
-    auto fail = [&](int code, const char* what) {
-        if (errbuf && errcap) { std::strncpy(errbuf, what, errcap - 1); errbuf[errcap - 1] = 0; }
-        return code;
-    };
-    try {
-        vxh::VxaModel vxa = vxh::read_vxa(xml, len, variant);
-        if (!vxa.unsupported.empty()) return fail(VXH_ERR_UNSUPPORTED, vxa.unsupported.front().c_str());
-        const vxh::RobotModel m = vxh::build_robot(vxa);
+    return inspected(xml, len, variant, errbuf, errcap, [&](const vxh::RobotModel& m) -> const char* {
         std::vector<double> ex;
         vxh::mesh_angle_excess(m, nullptr, nullptr, nullptr, ex);
         *count_out = (int)ex.size();
         for (int k = 0; k < std::min((int)ex.size(), capacity); ++k) out[k] = ex[k];
-        return VXH_OK;
-    } catch (const std::exception& ex) {
-        return fail(VXH_ERR_PARSE, ex.what());
-    }
+        return nullptr;
+    });
 }
 
 int vxh_get_state(const vxh_engine* ce, int robot, double* out14n, int capacity)

@@ -8,26 +8,18 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <atomic>
-#include <exception>
-#include <fstream>
-#include <mutex>
 #include <sstream>
 #include <stdexcept>
-#include <thread>
 
 #include "batch.hpp"
 #include "engine.hpp"
+#include "import.hpp"
 #include "kernels.hpp"
 #include "launch.hpp"
 
 namespace vxh {
 
-namespace {
-
 #define HIP_OK(call) hip_check((call), #call)
-
-}  // namespace
 
 int hip_device_count()
 {
@@ -176,11 +168,25 @@ struct Engine::Device {
         if (n == 0) n = 1;
         return (T*)raw_alloc(n * sizeof(T));
     }
-    void free_all()
+    // every stream of this engine idle, no sticky error: the state a failed call must leave behind, and what freeing a batch waits for
+    void idle()
     {
-        if (h_rstate) { hipHostFree(h_rstate); h_rstate = nullptr; h_rstate_cap = 0; }
+        for (hipStream_t st : group_streams) (void)hipStreamSynchronize(st);
+        if (tile_stream) (void)hipStreamSynchronize(tile_stream);
+        if (stream) (void)hipStreamSynchronize(stream);
+        (void)hipGetLastError();
+    }
+    void drop_graph()
+    {
         if (graph_exec) { hipGraphExecDestroy(graph_exec); graph_exec = nullptr; }
         if (graph) { hipGraphDestroy(graph); graph = nullptr; }
+    }
+    // (the allocations are freed in the order of `stream` alone, their consumers ran on the group and tile streams too: idle() first)
+    void free_all()
+    {
+        if (!allocs.empty()) idle();
+        if (h_rstate) { hipHostFree(h_rstate); h_rstate = nullptr; h_rstate_cap = 0; }
+        drop_graph();
         if (async_alloc && stream) { for (void* p : allocs) hipFreeAsync(p, stream); if (!allocs.empty()) hipStreamSynchronize(stream); }
         else for (void* p : allocs) hipFree(p);
         allocs.clear();
@@ -189,6 +195,18 @@ struct Engine::Device {
         results = nullptr;
         B = DBatch{};
     }
+    ~Device()                             // (the owner has made the device current)
+    {
+        free_all();
+        for (hipEvent_t ev : {ev0, ev1, tile_t0, tile_t1}) if (ev) hipEventDestroy(ev);
+        for (hipStream_t st : {stream, tile_stream}) if (st) hipStreamDestroy(st);
+        for (hipStream_t st : group_streams) hipStreamDestroy(st);
+        for (hipEvent_t ev : group_events) hipEventDestroy(ev);
+    }
+#ifdef VXH_PHASE_TIMING
+    void report_contact_rows(const std::vector<RobotModel>& robots);      // the developer build's report of a batch (Engine::clear)
+    void report_phase_counters();
+#endif
 };
 
 Engine::Engine(int variant, int device_id) : variant_(variant), device_id_(device_id), dev_(new Device)
@@ -236,24 +254,10 @@ Engine::Engine(int variant, int device_id) : variant_(variant), device_id_(devic
     }
 }
 
-Engine::~Engine()
-{
-    if (dev_) {
-        hipSetDevice(device_id_);
-        dev_->free_all();
-        if (dev_->ev0) hipEventDestroy(dev_->ev0);
-        if (dev_->ev1) hipEventDestroy(dev_->ev1);
-        if (dev_->stream) hipStreamDestroy(dev_->stream);
-        if (dev_->tile_stream) hipStreamDestroy(dev_->tile_stream);
-        if (dev_->tile_t0) hipEventDestroy(dev_->tile_t0);
-        if (dev_->tile_t1) hipEventDestroy(dev_->tile_t1);
-        for (hipStream_t st : dev_->group_streams) hipStreamDestroy(st);
-        for (hipEvent_t ev : dev_->group_events) hipEventDestroy(ev);
-    }
-}
+Engine::~Engine() { if (dev_) hipSetDevice(device_id_); }      // (~Device frees the batch, the streams and the events)
 
-// The add_* calls are build_* (parse + model building: may throw, touch nothing) followed by append(): a refused call leaves the
-// engine -- and, behind a handle over several devices, the distribution of the robots -- as it was.
+// The add_* calls are the build_* functions of import.hpp (parse + model building: may throw, touch nothing) followed by append(): a
+// refused call leaves the engine -- and, behind a handle over several devices, the distribution of the robots -- as it was.
 int Engine::append(std::vector<RobotModel>&& built)
 {
     const int first = (int)robots_.size();
@@ -262,165 +266,17 @@ int Engine::append(std::vector<RobotModel>&& built)
     state_downloaded_ = control_downloaded_ = reduced_downloaded_ = false;
     return first;
 }
-
-std::vector<RobotModel> Engine::build_vxa(const char* data, size_t len) const
-{
-    VxaModel vxa = read_vxa(data, len, variant_);
-    if (opt_.shape_descriptors) vxa.want_mesh = true;
-    if (!vxa.unsupported.empty()) {
-        std::string msg = "unsupported .vxa feature(s):";
-        for (const auto& u : vxa.unsupported) msg += " [" + u + "]";
-        throw std::invalid_argument(msg);
-    }
-    std::vector<RobotModel> out;
-    out.push_back(build_robot(vxa));
-    return out;
-}
-int Engine::add_vxa(const char* data, size_t len) { return append(build_vxa(data, len)); }
-int Engine::add_vxa_files(const std::vector<std::string>& paths) { return append(build_vxa_files(paths)); }
+int Engine::add_vxa(const char* data, size_t len) { return append(build_vxa(data, len, variant_, wants_mesh())); }
+int Engine::add_vxa_files(const std::vector<std::string>& paths) { return append(build_vxa_files(paths, variant_, wants_mesh())); }
 int Engine::add_arrays(const char* template_vxa, size_t len, const vxh_robot_arrays* in, int n, bool round_like_text)
-{ return append(build_arrays(template_vxa, len, in, n, round_like_text)); }
+{ return append(build_arrays(template_vxa, len, in, n, round_like_text, variant_, wants_mesh())); }
 
-// A generation arrives as hundreds of .vxa files; reading, XML parsing and model building (hop-distance lists, bond
-// classes, drag mesh) are independent per robot and take longer than the GPU needs to simulate them, so they are
-// spread over the host cores.  Robots are appended in the order of `paths`; the first failure (in that order) is
-// rethrown and nothing is appended.
-std::vector<RobotModel> Engine::build_vxa_files(const std::vector<std::string>& paths) const
+// no batch prepared, nothing downloaded, no step taken (the robots stay)
+void Engine::forget_batch()
 {
-    const int n = (int)paths.size();
-    std::vector<RobotModel> built(n);
-    std::vector<std::exception_ptr> errors(n);
-    std::atomic<int> next{0};
-    auto worker = [&]() {
-        for (int i = next.fetch_add(1); i < n; i = next.fetch_add(1)) {
-            try {
-                std::ifstream in(paths[i], std::ios::binary);
-                if (!in) throw std::runtime_error("io: cannot open " + paths[i]);
-                std::stringstream ss;
-                ss << in.rdbuf();
-                const std::string text = ss.str();
-                VxaModel vxa = read_vxa(text.data(), text.size(), variant_);
-                if (opt_.shape_descriptors) vxa.want_mesh = true;
-                if (!vxa.unsupported.empty()) {
-                    std::string msg = "unsupported .vxa feature(s):";
-                    for (const auto& u : vxa.unsupported) msg += " [" + u + "]";
-                    throw std::invalid_argument(msg + " in " + paths[i]);
-                }
-                built[i] = build_robot(vxa);
-            } catch (...) {
-                errors[i] = std::current_exception();
-            }
-        }
-    };
-    // 32 workers: on the 256-thread MI355X host 512 robots import in 15 ms with 32 threads and in 200 ms with 64 (allocator contention)
-    const int nthreads = std::max(1, std::min({n, (int)std::thread::hardware_concurrency(), 32}));
-    std::vector<std::thread> pool;
-    for (int t = 1; t < nthreads; ++t) pool.emplace_back(worker);
-    worker();
-    for (auto& t : pool) t.join();
-    for (int i = 0; i < n; ++i) if (errors[i]) std::rethrow_exception(errors[i]);
-    return built;
-}
-
-// A generation handed over as arrays (vxh_add_robots): one parsed template + per-robot lattice and layers.  The VxaModel of a robot
-// is exactly what read_vxa builds from the file the writer would have produced: material digits as they are, layer values taken by
-// occupied-voxel counter in file order (VX_Object.cpp:1879-1900), optionally through the writer's decimal text.
-std::vector<RobotModel> Engine::build_arrays(const char* template_vxa, size_t len, const vxh_robot_arrays* in, int n, bool round_like_text) const
-{
-    return build_models(models_from_arrays(template_vxa, len, in, n, round_like_text));
-}
-
-// ... in two steps: the cheap one (template parse, argument checks, the arrays copied into .vxa models: everything that can be
-// REFUSED) and the expensive one (model building).  A handle that pipelines a generation does the first when the robots are
-// added and the second chunk by chunk while earlier chunks already step (EngineSet::run).
-std::vector<RobotModel> Engine::build_models(std::vector<VxaModel>&& models) const
-{
-    const int n = (int)models.size();
-    std::vector<RobotModel> built(n);
-    std::vector<std::exception_ptr> errors(n);
-    std::atomic<int> next{0};
-    auto worker = [&]() {
-        for (int i = next.fetch_add(1); i < n; i = next.fetch_add(1)) {
-            try { built[i] = build_robot(models[i]); } catch (...) { errors[i] = std::current_exception(); }
-        }
-    };
-    const int nthreads = std::max(1, std::min({n, (int)std::thread::hardware_concurrency(), 32}));
-    std::vector<std::thread> pool;
-    for (int t = 1; t < nthreads; ++t) pool.emplace_back(worker);
-    worker();
-    for (auto& t : pool) t.join();
-    for (int i = 0; i < n; ++i) if (errors[i]) std::rethrow_exception(errors[i]);
-    return built;
-}
-
-std::vector<VxaModel> Engine::models_from_arrays(const char* template_vxa, size_t len, const vxh_robot_arrays* in, int n, bool round_like_text) const
-{
-    VxaModel base = read_vxa(template_vxa, len, variant_);
-    if (opt_.shape_descriptors) base.want_mesh = true;
-    if (!base.unsupported.empty()) {
-        std::string msg = "unsupported .vxa feature(s):";
-        for (const auto& u : base.unsupported) msg += " [" + u + "]";
-        throw std::invalid_argument(msg + " in the template");
-    }
-    struct LayerSlot { const char* tag; bool VxaModel::*has; std::vector<double> VxaModel::*values; bool land_only; };
-    static const LayerSlot slots[] = {
-        {"PhaseOffset", &VxaModel::has_phase_offset, &VxaModel::phase_offset, false},
-        {"TempAmpDamp", &VxaModel::has_temp_amp_damp, &VxaModel::temp_amp_damp, false},
-        {"Stiffness", &VxaModel::has_stiffness, &VxaModel::stiffness, false},
-        {"FinalPhaseOffset", &VxaModel::has_final_phase_offset, &VxaModel::final_phase_offset, true},
-        {"FinalTempAmpDamp", &VxaModel::has_final_temp_amp_damp, &VxaModel::final_temp_amp_damp, true},
-        {"InitialVoxelSize", &VxaModel::has_initial_voxel_size, &VxaModel::initial_voxel_size, true},
-        {"FinalVoxelSize", &VxaModel::has_final_voxel_size, &VxaModel::final_voxel_size, true},
-        {"GrowthTime", &VxaModel::has_growth_time, &VxaModel::growth_time, true},
-        {"StartGrowthTime", &VxaModel::has_start_growth_time, &VxaModel::start_growth_time, true},
-    };
-    for (const auto& sl : slots) { base.*(sl.has) = false; (base.*(sl.values)).clear(); }
-    base.structure.clear();
-    std::vector<VxaModel> built(n);
-    std::vector<std::exception_ptr> errors(n);
-    std::atomic<int> next{0};
-    auto worker = [&]() {
-        for (int i = next.fetch_add(1); i < n; i = next.fetch_add(1)) {
-            try {
-                const vxh_robot_arrays& A = in[i];
-                if (A.nx < 1 || A.ny < 1 || A.nz < 1 || (long long)A.nx * A.ny * A.nz > (1LL << 26) || !A.material) throw std::invalid_argument("bad lattice");
-                if (A.n_layers < 0 || (A.n_layers > 0 && (!A.layer_tags || !A.layers))) throw std::invalid_argument("bad layer arrays");
-                for (int l = 0; l < A.n_layers; ++l) if (!A.layer_tags[l] || !A.layers[l]) throw std::invalid_argument("null layer tag or layer");
-                VxaModel m = base;
-                m.nx = A.nx; m.ny = A.ny; m.nz = A.nz;
-                const size_t cells = (size_t)A.nx * A.ny * A.nz;
-                m.structure.assign(A.material, A.material + cells);
-                for (size_t k = 0; k < cells; ++k)
-                    if (m.structure[k] >= m.palette.size()) throw std::invalid_argument("material index outside the palette");
-                if (A.fitness_file_name) m.fitness_file_name = A.fitness_file_name;
-                for (int l = 0; l < A.n_layers; ++l) {
-                    const LayerSlot* slot = nullptr;
-                    for (const auto& sl : slots) if (std::strcmp(sl.tag, A.layer_tags[l]) == 0) slot = &sl;
-                    if (!slot) throw std::invalid_argument(std::string("unsupported per-voxel layer <") + A.layer_tags[l] + ">");
-                    if (slot->land_only && variant_ != 0) throw std::invalid_argument(std::string("unsupported <") + A.layer_tags[l] + "> development layer (land_water)");
-                    std::vector<double>& out = m.*(slot->values);
-                    m.*(slot->has) = true;
-                    out.clear();
-                    for (size_t k = 0; k < cells; ++k) {
-                        if (m.structure[k] == 0) continue;
-                        double v = A.layers[l][k];
-                        if (round_like_text) { char buf[48]; std::snprintf(buf, sizeof(buf), "%.12g", v); v = std::atof(buf); }
-                        out.push_back(v);
-                    }
-                }
-                built[i] = std::move(m);
-            } catch (...) {
-                errors[i] = std::current_exception();
-            }
-        }
-    };
-    const int nthreads = std::max(1, std::min({n, (int)std::thread::hardware_concurrency(), 32}));
-    std::vector<std::thread> pool;
-    for (int t = 1; t < nthreads; ++t) pool.emplace_back(worker);
-    worker();
-    for (auto& t : pool) t.join();
-    for (int i = 0; i < n; ++i) if (errors[i]) std::rethrow_exception(errors[i]);
-    return built;
+    host_.clear();
+    prepared_ = state_downloaded_ = control_downloaded_ = reduced_downloaded_ = false;
+    rounds_done_ = 0;
 }
 
 std::vector<RobotModel> Engine::take_robots()
@@ -429,9 +285,7 @@ std::vector<RobotModel> Engine::take_robots()
     dev_->free_all();
     std::vector<RobotModel> out = std::move(robots_);
     robots_.clear();
-    host_.clear();
-    prepared_ = state_downloaded_ = control_downloaded_ = reduced_downloaded_ = false;
-    rounds_done_ = 0;
+    forget_batch();
     return out;
 }
 
@@ -443,83 +297,83 @@ void Engine::set_tiling_allowed(bool on)
     prepared_ = false;
 }
 
-void Engine::give_robots(std::vector<RobotModel>&& models)
+#ifdef VXH_PHASE_TIMING
+// The developer build's report of a batch that is about to go (scripts/dev_gpu_diag.py and scripts/tile_timeline_sum.py parse it)
+void Engine::Device::report_contact_rows(const std::vector<RobotModel>& robots)
 {
-    for (auto& m : models) robots_.push_back(std::move(m));
-    prepared_ = state_downloaded_ = control_downloaded_ = reduced_downloaded_ = false;
+    if (!std::getenv("VXH_COL_STATS") || B.col_rows <= 0) return;    // lengths of the contact rows as the last broad-phase runs left them
+    std::vector<int> cnt(B.col_rows);
+    HIP_OK(hipMemcpy(cnt.data(), B.col_cnt, sizeof(int) * cnt.size(), hipMemcpyDeviceToHost));
+    long long hist[9] = {0}, total = 0; int mx = 0;
+    for (int c : cnt) { total += c; mx = std::max(mx, c); ++hist[c == 0 ? 0 : std::min(8, 1 + (c - 1) / 8)]; }
+    fprintf(stderr, "contact rows: %zu surface voxels, %.1f partners on average, longest %d; rows by length 0 | 1-8 | 9-16 | ... | 57-64:", cnt.size(), (double)total / cnt.size(), mx);
+    for (long long v : hist) fprintf(stderr, " %lld", v);
+    long long per_robot_max = 0;
+    for (size_t r = 0; r < robots.size(); ++r) {
+        long long sum = 0;
+        const int b = surf_begin[r], n = robots[r].nsurf;
+        for (int i = 0; i < n; ++i) sum += cnt[b + i];
+        per_robot_max = std::max(per_robot_max, sum);
+    }
+    fprintf(stderr, "\n  most partners in one robot: %lld\n", per_robot_max);
 }
 
-void Engine::clear()
+void Engine::Device::report_phase_counters()
 {
-    HIP_OK(hipSetDevice(device_id_));
-#ifdef VXH_PHASE_TIMING
-    if (std::getenv("VXH_COL_STATS") && dev_->B.col_rows > 0) {    // lengths of the contact rows as the last broad-phase runs left them
-        std::vector<int> cnt(dev_->B.col_rows);
-        HIP_OK(hipMemcpy(cnt.data(), dev_->B.col_cnt, sizeof(int) * cnt.size(), hipMemcpyDeviceToHost));
-        long long hist[9] = {0}, total = 0; int mx = 0;
-        for (int c : cnt) { total += c; mx = std::max(mx, c); ++hist[c == 0 ? 0 : std::min(8, 1 + (c - 1) / 8)]; }
-        fprintf(stderr, "contact rows: %zu surface voxels, %.1f partners on average, longest %d; rows by length 0 | 1-8 | 9-16 | ... | 57-64:", cnt.size(), (double)total / cnt.size(), mx);
-        for (long long v : hist) fprintf(stderr, " %lld", v);
-        long long per_robot_max = 0, wave_max_sum = 0, waves = 0;
-        for (size_t r = 0; r < robots_.size(); ++r) {
-            long long sum = 0;
-            const int b = dev_->surf_begin[r], n = robots_[r].nsurf;
-            for (int i = 0; i < n; ++i) sum += cnt[b + i];
-            per_robot_max = std::max(per_robot_max, sum);
-        }
-        fprintf(stderr, "\n  most partners in one robot: %lld\n", per_robot_max);
-        (void)wave_max_sum; (void)waves;
-    }
-    if (dev_->B.prof) {
-        unsigned long long h[16 * 8 + 256 * 8];
-        HIP_OK(hipMemcpy(h, dev_->B.prof, sizeof(h), hipMemcpyDeviceToHost));
-        if (std::getenv("VXH_PROF_TILES")) {    // the first tiles at one step of the last launch: real-time counter (10 ns ticks) at the step's boundaries
-            unsigned long long t0 = ~0ull;
-            for (int t = 0; t < std::min(256, dev_->B.n_tiles); ++t) if (h[128 + t * 8]) t0 = std::min(t0, h[128 + t * 8]);
-            fprintf(stderr, "tile: top  halo-done  bond-done  voxel-done  C-passed | svc: barrier-resolved | next top | mv-published   (us after the first tile's top)\n");
-            for (int t = 0; t < std::min(256, dev_->B.n_tiles); ++t) {
-                fprintf(stderr, "tile %3d:", t);
-                for (int k : {0, 1, 2, 3, 4, 5, 6, 7}) fprintf(stderr, " %7.2f", 0.01 * (double)(long long)(h[128 + t * 8 + k] - t0));
-                fprintf(stderr, "\n");
-            }
-        }
-        if (h[2112]) fprintf(stderr, "contact rows in LDS: %llu wavefront copies, %llu did not fit (mean capacity %.0f pairs); cross-check (dbg 8): %llu lanes, %llu with different bits, %llu whose LDS row differs from memory; of the differing lanes: %llu with fewer mask bits than pairs in reach, %llu with more, %llu with as many\n",
-                            h[2112], h[2113], h[2114] ? (double)h[2114] * 12.0 / (double)h[2112] : 0.0, h[2115], h[2116], h[2117], h[2118], h[2119], h[2111]);
-        if (h[2108]) fprintf(stderr, "broad-phase runs (resident kernel, with the copy of the rows): %llu, %.0f cycles each on average; workgroup-launches with at least one: %llu; "
-                            "most cycles one workgroup spent in them in one launch (maximum over ALL launches): %llu\n", h[2108], (double)h[2109] / (double)h[2108], h[2107], h[2110]);
-        if (h[2108] && h[2100]) fprintf(stderr, "   of a broad-phase run, cycles on average (first wavefront): staging the surface list %.0f | its own scan / block pairs %.0f | wait for the "
-                                      "slowest wavefront %.0f | bit matrix -> rows %.0f | the rest (copy of the rows to LDS) %.0f\n", (double)h[2100] / h[2108], (double)h[2101] / h[2108], (double)h[2102] / h[2108],
-                                      (double)h[2126] / h[2108], ((double)h[2109] - (double)h[2100] - (double)h[2101] - (double)h[2102] - (double)h[2126]) / h[2108]);
-        if (h[2104]) fprintf(stderr, "   broad-phase cross-check (dbg 16): %llu rows built by both scans, %llu differ (%llu longer, %llu shorter than the plain scan's; longest row %llu against %llu; partners in all %llu against %llu)\n",
-                             h[2104], h[2105], h[2120], h[2121], h[2122], h[2123], h[2124], h[2125]);
-        if (h[2103]) fprintf(stderr, "   prologue of the resident kernel, cycle sums of the first thread over all workgroup-launches: tables + first barrier %.3e | state load, zeroing, "
-                             "first control %.3e | rows_to_lds %.3e  = (its parts, incl. the calls after broad-phase runs) ordinal -> count loads + barrier %.3e | scan + allotment %.3e | copy + barrier %.3e\n",
-                             (double)h[2103], (double)h[2106], (double)h[2113], (double)h[2114], (double)h[2115], (double)h[2116]);
-        if (h[2142]) fprintf(stderr, "   tiled kernel, voxel phase of the first thread of every tile, cycle sums: six-direction sums %.3e | contacts %.3e | voxel update %.3e | pose granules out %.3e\n",
-                             (double)h[2140], (double)h[2141], (double)h[2142], (double)h[2143]);
-        if (h[2131]) fprintf(stderr, "   drag, facet pass (first thread, cycle sums): barrier behind the vertices %.3e | facet loop %.3e | barrier %.3e | per-voxel sums %.3e | barrier %.3e\n",
-                             (double)h[2130], (double)h[2131], (double)h[2132], (double)h[2133], (double)h[2134]);
-        static const char* names[6] = {"ctl+barA", "aux", "bond", "barB", "voxel", "barC+pub"};
-        static const char* tnames[8] = {"halo-wait", "bond", "svc:poll", "barB", "latch/rebuild", "voxel", "barC+mv", "svc:reduce+horizon"};
-        const bool tiled = !dev_->tile_launches.empty();
-        if (tiled && h[121]) fprintf(stderr, "robot barrier: %.2f poll rounds per barrier, %.0f cycles per barrier\n", (double)h[120] / h[121], (double)h[122] / h[121]);
-        for (int w = 0; w < 15; ++w) {
-            double tot = 0; for (int k = 0; k < (tiled ? 8 : 6); ++k) tot += (double)h[w * 8 + k];
-            if (tot == 0) continue;
-            fprintf(stderr, "wave %2d:", w);
-            if (tiled) for (int k = 0; k < 8; ++k) fprintf(stderr, " %s %5.1f%%", tnames[k], 100.0 * h[w * 8 + k] / tot);
-            else for (int k = 0; k < 6; ++k) fprintf(stderr, " %s %5.1f%%", names[k], 100.0 * h[w * 8 + k] / tot);
-            fprintf(stderr, "  total %.3e cycles", tot);
-            if (!tiled && h[w * 8 + 6] + h[w * 8 + 7]) fprintf(stderr, "  (MESH: mesh vertices / facets inside aux; else: before the step loop / after it, cycles)  %.3e  %.3e", (double)h[w * 8 + 6], (double)h[w * 8 + 7]);
+    if (!B.prof) return;
+    unsigned long long h[16 * 8 + 256 * 8];
+    HIP_OK(hipMemcpy(h, B.prof, sizeof(h), hipMemcpyDeviceToHost));
+    if (std::getenv("VXH_PROF_TILES")) {    // the first tiles at one step of the last launch: real-time counter (10 ns ticks) at the step's boundaries
+        unsigned long long t0 = ~0ull;
+        for (int t = 0; t < std::min(256, B.n_tiles); ++t) if (h[128 + t * 8]) t0 = std::min(t0, h[128 + t * 8]);
+        fprintf(stderr, "tile: top  halo-done  bond-done  voxel-done  C-passed | svc: barrier-resolved | next top | mv-published   (us after the first tile's top)\n");
+        for (int t = 0; t < std::min(256, B.n_tiles); ++t) {
+            fprintf(stderr, "tile %3d:", t);
+            for (int k : {0, 1, 2, 3, 4, 5, 6, 7}) fprintf(stderr, " %7.2f", 0.01 * (double)(long long)(h[128 + t * 8 + k] - t0));
             fprintf(stderr, "\n");
         }
     }
+    if (h[2112]) fprintf(stderr, "contact rows in LDS: %llu wavefront copies, %llu did not fit (mean capacity %.0f pairs); cross-check (dbg 8): %llu lanes, %llu with different bits, %llu whose LDS row differs from memory; of the differing lanes: %llu with fewer mask bits than pairs in reach, %llu with more, %llu with as many\n",
+                        h[2112], h[2113], h[2114] ? (double)h[2114] * 12.0 / (double)h[2112] : 0.0, h[2115], h[2116], h[2117], h[2118], h[2119], h[2111]);
+    if (h[2108]) fprintf(stderr, "broad-phase runs (resident kernel, with the copy of the rows): %llu, %.0f cycles each on average; workgroup-launches with at least one: %llu; "
+                        "most cycles one workgroup spent in them in one launch (maximum over ALL launches): %llu\n", h[2108], (double)h[2109] / (double)h[2108], h[2107], h[2110]);
+    if (h[2108] && h[2100]) fprintf(stderr, "   of a broad-phase run, cycles on average (first wavefront): staging the surface list %.0f | its own scan / block pairs %.0f | wait for the "
+                                  "slowest wavefront %.0f | bit matrix -> rows %.0f | the rest (copy of the rows to LDS) %.0f\n", (double)h[2100] / h[2108], (double)h[2101] / h[2108], (double)h[2102] / h[2108],
+                                  (double)h[2126] / h[2108], ((double)h[2109] - (double)h[2100] - (double)h[2101] - (double)h[2102] - (double)h[2126]) / h[2108]);
+    if (h[2104]) fprintf(stderr, "   broad-phase cross-check (dbg 16): %llu rows built by both scans, %llu differ (%llu longer, %llu shorter than the plain scan's; longest row %llu against %llu; partners in all %llu against %llu)\n",
+                         h[2104], h[2105], h[2120], h[2121], h[2122], h[2123], h[2124], h[2125]);
+    if (h[2103]) fprintf(stderr, "   prologue of the resident kernel, cycle sums of the first thread over all workgroup-launches: tables + first barrier %.3e | state load, zeroing, "
+                         "first control %.3e | rows_to_lds %.3e  = (its parts, incl. the calls after broad-phase runs) ordinal -> count loads + barrier %.3e | scan + allotment %.3e | copy + barrier %.3e\n",
+                         (double)h[2103], (double)h[2106], (double)h[2113], (double)h[2114], (double)h[2115], (double)h[2116]);
+    if (h[2142]) fprintf(stderr, "   tiled kernel, voxel phase of the first thread of every tile, cycle sums: six-direction sums %.3e | contacts %.3e | voxel update %.3e | pose granules out %.3e\n",
+                         (double)h[2140], (double)h[2141], (double)h[2142], (double)h[2143]);
+    if (h[2131]) fprintf(stderr, "   drag, facet pass (first thread, cycle sums): barrier behind the vertices %.3e | facet loop %.3e | barrier %.3e | per-voxel sums %.3e | barrier %.3e\n",
+                         (double)h[2130], (double)h[2131], (double)h[2132], (double)h[2133], (double)h[2134]);
+    static const char* names[6] = {"ctl+barA", "aux", "bond", "barB", "voxel", "barC+pub"};
+    static const char* tnames[8] = {"halo-wait", "bond", "svc:poll", "barB", "latch/rebuild", "voxel", "barC+mv", "svc:reduce+horizon"};
+    const bool tiled = !tile_launches.empty();
+    if (tiled && h[121]) fprintf(stderr, "robot barrier: %.2f poll rounds per barrier, %.0f cycles per barrier\n", (double)h[120] / h[121], (double)h[122] / h[121]);
+    for (int w = 0; w < 15; ++w) {
+        double tot = 0; for (int k = 0; k < (tiled ? 8 : 6); ++k) tot += (double)h[w * 8 + k];
+        if (tot == 0) continue;
+        fprintf(stderr, "wave %2d:", w);
+        if (tiled) for (int k = 0; k < 8; ++k) fprintf(stderr, " %s %5.1f%%", tnames[k], 100.0 * h[w * 8 + k] / tot);
+        else for (int k = 0; k < 6; ++k) fprintf(stderr, " %s %5.1f%%", names[k], 100.0 * h[w * 8 + k] / tot);
+        fprintf(stderr, "  total %.3e cycles", tot);
+        if (!tiled && h[w * 8 + 6] + h[w * 8 + 7]) fprintf(stderr, "  (MESH: mesh vertices / facets inside aux; else: before the step loop / after it, cycles)  %.3e  %.3e", (double)h[w * 8 + 6], (double)h[w * 8 + 7]);
+        fprintf(stderr, "\n");
+    }
+}
 #endif
-    dev_->free_all();
-    robots_.clear();
-    host_.clear();
-    prepared_ = state_downloaded_ = control_downloaded_ = reduced_downloaded_ = false;
-    rounds_done_ = 0;
+
+void Engine::clear()
+{
+#ifdef VXH_PHASE_TIMING
+    HIP_OK(hipSetDevice(device_id_));
+    dev_->report_contact_rows(robots_);
+    dev_->report_phase_counters();
+#endif
+    take_robots();
 }
 
 // A captured step graph holds the kernel arguments (the whole DBatch, by value) of the moment it was captured: every option that
@@ -527,8 +381,7 @@ void Engine::clear()
 void Engine::drop_graph()
 {
     HIP_OK(hipSetDevice(device_id_));
-    if (dev_->graph_exec) { hipGraphExecDestroy(dev_->graph_exec); dev_->graph_exec = nullptr; }
-    if (dev_->graph) { hipGraphDestroy(dev_->graph); dev_->graph = nullptr; }
+    dev_->drop_graph();
 }
 
 // The options of vxh_set_option, each described once.  A FLAG is stored as value != 0, an INT truncated.  Accepted values: ANY, the WHOLE
@@ -767,10 +620,8 @@ void Engine::prepare()
     D.robot_tiled = std::move(P.robot_tiled); D.robot_tiles = std::move(P.robot_tiles);
     hs.mark("kernel choice, tiling, launch groups");
     hs.print("prepare");
+    forget_batch();
     prepared_ = true;
-    state_downloaded_ = control_downloaded_ = reduced_downloaded_ = false;
-    host_.clear();
-    rounds_done_ = 0;
     counters_ = vxh_counters{};
 }
 
@@ -792,8 +643,7 @@ void Engine::advance(long long max_rounds)
 {
     const long long before = rounds_done_;
     try {
-        advance_launch(max_rounds);
-        advance_finish();
+        launch_and_finish(max_rounds);
     } catch (const TileTimeout& e) {
         // The tiles of a robot are co-resident workgroups that wait for each other: a second process on the GPU can keep some of them
         // off the chip until the bounded spins give up.  The robots' state of before the call is gone -- but the evaluation is a
@@ -805,29 +655,25 @@ void Engine::advance(long long max_rounds)
         if (opt_.tiled == 0 || !tiling_allowed_) throw;
         std::fprintf(stderr, "vxhip: %s -- this batch is stepped again%s without the tiled kernel, which stays off for this engine\n", e.what(),
                      before != 0 ? " from its imported state" : "");
-        dev_->pending.active = false;
         opt_.tiled = 0;
         prepare();
         const long long huge = 0x7fffffffffffffffLL / 4;
-        advance_launch(max_rounds >= huge - before ? huge : before + max_rounds);
-        advance_finish();
-    } catch (...) {
-        // a launch sequence that ended halfway (a refused kernel, a HIP error): nothing of it may still be queued when the caller goes on
-        quiesce();
-        throw;
+        launch_and_finish(max_rounds >= huge - before ? huge : before + max_rounds);
     }
 }
 
-// every stream of this engine idle, no launched call pending, no sticky error: the state a failed call leaves behind
+// a launch sequence that ended halfway (a refused kernel, a HIP error, a tile timeout): nothing of it may still be queued when the caller goes on
+void Engine::launch_and_finish(long long max_rounds)
+{
+    try { advance_launch(max_rounds); advance_finish(); }
+    catch (...) { quiesce(); throw; }
+}
+
 void Engine::quiesce()
 {
-    Device& D = *dev_;
     (void)hipSetDevice(device_id_);
-    for (hipStream_t st : D.group_streams) (void)hipStreamSynchronize(st);
-    if (D.tile_stream) (void)hipStreamSynchronize(D.tile_stream);
-    if (D.stream) (void)hipStreamSynchronize(D.stream);
-    (void)hipGetLastError();
-    D.pending.active = false;
+    dev_->idle();
+    dev_->pending.active = false;
 }
 
 void Engine::advance_launch(long long max_rounds)
@@ -919,8 +765,7 @@ void Engine::advance_launch(long long max_rounds)
         long long launched = 0;
         if (opt_.graph_steps > 1 && cap == cap_all && todo >= opt_.graph_steps) {
             if (!D.graph_exec || D.graph_rounds != opt_.graph_steps || D.graph_mask != B.streamed) {
-                if (D.graph_exec) { hipGraphExecDestroy(D.graph_exec); D.graph_exec = nullptr; }
-                if (D.graph) { hipGraphDestroy(D.graph); D.graph = nullptr; }
+                D.drop_graph();
                 HIP_OK(hipStreamBeginCapture(D.stream, hipStreamCaptureModeThreadLocal));
                 for (int k = 0; k < opt_.graph_steps; ++k) round(cap_all);
                 HIP_OK(hipStreamEndCapture(D.stream, &D.graph));
@@ -955,80 +800,36 @@ void Engine::advance_finish()
     HIP_OK(hipSetDevice(device_id_));
     Device& D = *dev_;
     if (!D.pending.active) return;
-    D.pending.active = false;
-    const long long todo = D.pending.todo, launches = D.pending.launches, tile_launch_count = D.pending.tile_launch_count;
-    const bool fused = D.pending.fused, tiled = D.pending.tiled, streaming = D.pending.streaming;
-    const std::vector<int>& steps_before = D.pending.steps_before;
-    const std::vector<long long>& group_launches = D.pending.group_launches;
+    Device::Pending& P = D.pending;
+    P.active = false;
     HostStages hs;
     HIP_OK(hipStreamSynchronize(D.stream));
     float ms = 0;
     HIP_OK(hipEventElapsedTime(&ms, D.ev0, D.ev1));
     counters_.kernel_seconds += ms * 1e-3;
-    counters_.launches += launches;
-    rounds_done_ += todo;
+    counters_.launches += P.launches;
+    rounds_done_ += P.todo;
     state_downloaded_ = reduced_downloaded_ = false;
     hs.mark("wait for the GPU");
     download_control(true);
     hs.mark("control blocks back");
-
-    // dominant kernel of this call: the launch group that processed most voxel-steps (fused) / the whole call (streaming)
-    std::vector<double> grp_vs(D.groups.size(), 0.0), grp_ab(D.groups.size(), 0.0);
-    double all_vs = 0, all_ab = 0;
-    auto work = [&](int r, double& vs, double& ab) {
-        const double ds = host_[r].steps - steps_before[r];
-        vs += ds * robots_[r].nvox; ab += ds * (224.0 * robots_[r].nvox + 144.0 * robots_[r].nbond);
-    };
-    for (size_t r = 0; r < robots_.size(); ++r) if (robots_[r].nvox) work((int)r, all_vs, all_ab);
-    double tile_vs = 0, tile_ab = 0;                        // what the tiled kernel did
-    int n_tiled = 0;
-    for (size_t r = 0; r < robots_.size(); ++r) if (D.robot_tiled[r]) { work((int)r, tile_vs, tile_ab); ++n_tiled; }
-    double grp_best = 0;
-    if (fused) for (size_t k = 0; k < D.groups.size(); ++k) { double v = 0, a = 0; for (int r : D.groups[k].robots) work(r, v, a); grp_best = std::max(grp_best, v); }
-    if (tiled && tile_vs >= grp_best && tile_vs >= all_vs - tile_vs - grp_best) {
-        float cms = 0;
-        HIP_OK(hipEventElapsedTime(&cms, D.tile_t0, D.tile_t1));
-        counters_.dominant_block = 1;                      // (1 = k_tile_steps; the resident kernel reports its workgroup size)
-        counters_.dominant_robots = n_tiled;
-        counters_.dominant_launches = tile_launch_count; counters_.dominant_seconds = cms * 1e-3;
-        counters_.dominant_alg_bytes = tile_ab; counters_.dominant_voxel_steps = tile_vs;
-    } else if (fused && !D.groups.empty()) {
-        size_t best = 0;
-        for (size_t k = 0; k < D.groups.size(); ++k) {
-            for (int r : D.groups[k].robots) work(r, grp_vs[k], grp_ab[k]);
-            if (grp_vs[k] > grp_vs[best]) best = k;
-        }
-        double rest_vs = all_vs - tile_vs, rest_ab = all_ab - tile_ab;   // what the streaming kernels did next to the groups
-        for (size_t k = 0; k < D.groups.size(); ++k) { rest_vs -= grp_vs[k]; rest_ab -= grp_ab[k]; }
-        if (streaming && rest_vs > grp_vs[best]) {
-            counters_.dominant_block = 0; counters_.dominant_robots = D.n_rest;
-            counters_.dominant_launches = todo; counters_.dominant_seconds = ms * 1e-3;
-            counters_.dominant_alg_bytes = rest_ab; counters_.dominant_voxel_steps = rest_vs;
-        } else {
-            float cms = 0;
-            if (D.pending.single) cms = ms; else HIP_OK(hipEventElapsedTime(&cms, D.groups[best].t0, D.groups[best].t1));
-            // (the resident kernel's workgroup size; + 1: the wide kernel)
-            counters_.dominant_block = D.groups[best].block + (D.groups[best].wide ? 1 : 0); counters_.dominant_robots = D.groups[best].count;
-            counters_.dominant_launches = group_launches[best]; counters_.dominant_seconds = cms * 1e-3;
-            counters_.dominant_alg_bytes = grp_ab[best]; counters_.dominant_voxel_steps = grp_vs[best];
-        }
-    } else {
-        counters_.dominant_block = 0; counters_.dominant_robots = (int)robots_.size() - n_tiled;
-        counters_.dominant_launches = todo; counters_.dominant_seconds = ms * 1e-3;
-        counters_.dominant_alg_bytes = all_ab - tile_ab; counters_.dominant_voxel_steps = all_vs - tile_vs;
-    }
+    // dominant kernel of this call (batch.cpp decides which unit; here: the pair of events that timed it)
+    std::vector<int>& steps = P.steps_before;                  // (from here on: the steps this call took)
+    for (size_t r = 0; r < robots_.size(); ++r) steps[r] = host_[r].steps - steps[r];
+    std::vector<const GroupPlan*> groups;
+    for (const Device::Group& g : D.groups) groups.push_back(&g);
+    const DominantKernel dom = dominant_kernel(robots_, steps, groups, D.robot_tiled, P.fused, P.tiled, P.streaming, D.n_rest, P.todo, P.group_launches, P.tile_launch_count);
+    float cms = ms;
+    if (dom.unit == DominantKernel::TILES) HIP_OK(hipEventElapsedTime(&cms, D.tile_t0, D.tile_t1));
+    else if (dom.unit == DominantKernel::GROUP && !P.single) HIP_OK(hipEventElapsedTime(&cms, D.groups[dom.group].t0, D.groups[dom.group].t1));
+    counters_.dominant_block = dom.block; counters_.dominant_robots = dom.robots;
+    counters_.dominant_launches = dom.launches; counters_.dominant_seconds = cms * 1e-3;
+    counters_.dominant_alg_bytes = dom.alg_bytes; counters_.dominant_voxel_steps = dom.voxel_steps;
     hs.mark("accounting");
     hs.print("advance_finish");
 }
 
-void Engine::run()
-{
-    auto t0 = std::chrono::steady_clock::now();
-    if (robots_.empty()) return;
-    if (!prepared_) prepare();
-    advance(0x7fffffffffffffffLL / 4);
-    counters_.run_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-}
+void Engine::run() { step(0x7fffffffffffffffLL / 4); }
 
 void Engine::run_launch()
 {

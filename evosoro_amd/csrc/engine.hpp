@@ -58,12 +58,6 @@ public:
     int add_vxa(const char* data, size_t len);              // returns robot index; throws
     int add_vxa_files(const std::vector<std::string>& paths);   // parse + build on all host cores, append in order; returns first index
     int add_arrays(const char* template_vxa, size_t len, const vxh_robot_arrays* robots, int n, bool round_like_text);   // returns first index
-    // the same in two steps: parse + build (throws, changes nothing), then append
-    std::vector<RobotModel> build_vxa(const char* data, size_t len) const;
-    std::vector<RobotModel> build_vxa_files(const std::vector<std::string>& paths) const;
-    std::vector<RobotModel> build_arrays(const char* template_vxa, size_t len, const vxh_robot_arrays* robots, int n, bool round_like_text) const;
-    std::vector<VxaModel> models_from_arrays(const char* template_vxa, size_t len, const vxh_robot_arrays* robots, int n, bool round_like_text) const;   // checks + copies
-    std::vector<RobotModel> build_models(std::vector<VxaModel>&& models) const;                                                                 // the expensive part
     int append(std::vector<RobotModel>&& built);             // returns first index
     int num_robots() const { return (int)robots_.size(); }
     const RobotModel& robot(int i) const { return robots_[i]; }
@@ -84,6 +78,7 @@ public:
     void set_option(const std::string& key, double value);
     void check_option(const std::string& key, double value) const;   // throws what set_option would throw, changes nothing
     int variant() const { return variant_; }
+    bool wants_mesh() const { return opt_.shape_descriptors != 0; }   // robots added now carry the surface mesh (import.hpp: want_mesh)
     int device() const { return device_id_; }
     // EngineSet moves robots between the engines of a handle (host-side models only; the batch is rebuilt on the next run)
     std::vector<RobotModel> take_robots();
@@ -92,7 +87,7 @@ public:
     // its value and acts again when the veto is lifted (EngineSet::gather / clear).
     void set_tiling_allowed(bool on);
     void add_run_seconds(double s) { counters_.run_seconds += s; }
-    void give_robots(std::vector<RobotModel>&& models);
+    void give_robots(std::vector<RobotModel>&& models) { append(std::move(models)); }
     void drop_graph();
 
 private:
@@ -101,7 +96,9 @@ private:
     void advance(long long max_rounds);        // launch step rounds and wait
     void advance_launch(long long max_rounds);
     void advance_finish();
+    void launch_and_finish(long long max_rounds);   // the two, and quiesce() before any failure leaves
     void quiesce();                            // after a launch sequence that failed halfway: every stream idle, nothing pending
+    void forget_batch();                       // no batch prepared, nothing downloaded, no step taken
     void download();
     void download_control(bool already_copied = false);
     void download_reduced();                   // k_results + the traces: what results need, without the voxel state

@@ -7,6 +7,7 @@
 #include <thread>
 
 #include "engine.hpp"
+#include "import.hpp"
 
 namespace vxh {
 
@@ -35,7 +36,7 @@ void EngineSet::tiling_allowed_again() { for (auto& e : engines_) e->set_tiling_
 void EngineSet::flush_pending()
 {
     if (pending_.empty()) return;
-    std::vector<RobotModel> m = engines_[0]->build_models(std::move(pending_));
+    std::vector<RobotModel> m = build_models(std::move(pending_));
     pending_.clear();
     gather();
     engines_[0]->append(std::move(m));
@@ -104,18 +105,18 @@ void EngineSet::each(const std::function<void(Engine&)>& body)
 // additions: parse and build first -- a refused call (bad file, unsupported feature) leaves the robots where they are, with the
 // results of earlier runs readable -- then bring every robot back to engine 0 and append
 int EngineSet::add_vxa(const char* data, size_t len)
-{ std::vector<RobotModel> m = engines_[0]->build_vxa(data, len); flush_pending(); gather(); return engines_[0]->append(std::move(m)); }
+{ std::vector<RobotModel> m = build_vxa(data, len, engines_[0]->variant(), engines_[0]->wants_mesh()); flush_pending(); gather(); return engines_[0]->append(std::move(m)); }
 int EngineSet::add_vxa_files(const std::vector<std::string>& paths)
-{ std::vector<RobotModel> m = engines_[0]->build_vxa_files(paths); flush_pending(); gather(); return engines_[0]->append(std::move(m)); }
+{ std::vector<RobotModel> m = build_vxa_files(paths, engines_[0]->variant(), engines_[0]->wants_mesh()); flush_pending(); gather(); return engines_[0]->append(std::move(m)); }
 int EngineSet::add_arrays(const char* t, size_t len, const vxh_robot_arrays* robots, int n, bool round_like_text)
 {
     if (pipelined_ && !distributed_ && engines_[0]->num_robots() == 0) {     // a fresh generation on a pipelining handle: check + copy now, build at the run
-        std::vector<VxaModel> m = engines_[0]->models_from_arrays(t, len, robots, n, round_like_text);
+        std::vector<VxaModel> m = models_from_arrays(t, len, robots, n, round_like_text, engines_[0]->variant(), engines_[0]->wants_mesh());
         const int first = (int)pending_.size();
         for (auto& x : m) pending_.push_back(std::move(x));
         return first;
     }
-    std::vector<RobotModel> m = engines_[0]->build_arrays(t, len, robots, n, round_like_text);
+    std::vector<RobotModel> m = build_arrays(t, len, robots, n, round_like_text, engines_[0]->variant(), engines_[0]->wants_mesh());
     flush_pending(); gather();
     return engines_[0]->append(std::move(m));
 }
@@ -149,7 +150,7 @@ void EngineSet::run()
                 // one engine owns the device: its own run(), i.e. with the tiled kernel and with the fall-back of a tile timeout
                 // (Engine::advance: the batch is stepped again without that kernel), and its own accounting of the run's wall time
                 tiling_allowed_again();
-                engines_[0]->append(engines_[0]->build_models(std::move(all)));
+                engines_[0]->append(build_models(std::move(all)));
                 for (int i = 0; i < n; ++i) where_[i] = {0, i};
                 distributed_ = true;
                 engines_[0]->run();
@@ -160,7 +161,7 @@ void EngineSet::run()
                 const int lo = (int)((long long)n * k / K), hi = (int)((long long)n * (k + 1) / K);
                 if (hi <= lo) continue;
                 std::vector<VxaModel> chunk(std::make_move_iterator(all.begin() + lo), std::make_move_iterator(all.begin() + hi));
-                engines_[k]->append(engines_[k]->build_models(std::move(chunk)));
+                engines_[k]->append(build_models(std::move(chunk)));
                 for (int i = lo; i < hi; ++i) where_[i] = {k, i - lo};
                 engines_[k]->run_launch();
                 launched = k + 1;

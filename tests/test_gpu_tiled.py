@@ -391,6 +391,44 @@ def test_a_tile_kernel_that_needs_scratch_is_refused_before_it_is_launched(golde
         assert np.abs(eng.state(0)[:, :8] - tiled[:, :8]).max() < 1e-12
 
 
+def test_a_refusal_behind_enqueued_group_kernels_leaves_a_usable_engine(tmp_path, monkeypatch):
+    """The refused launch in a MIXED batch: small robots (launch groups on their own streams) next to a lattice above 1024 voxels (tiled).
+    With the tolerated scratch size below zero the call fails with VXH_ERR_HIP when it reaches the tile launch -- the group kernels of the
+    small robots are enqueued by then.  reset() frees the batch those kernels read: the engine waits for every one of its streams first
+    (Device::idle), not only for the stream it frees on.  Every robot must then come out as in an engine that never failed."""
+    from evosoro_amd import engine as eng_mod, workloads
+    from evosoro_amd.base import Sim, Env
+    from evosoro_amd.tools.read_write_voxelyze import write_voxelyze_file
+    os.makedirs(tmp_path / "voxelyzeFiles")
+    sim = Sim(dt_frac=0.9, simulation_time=0.05, fitness_eval_init_time=0.01)
+    inds = [workloads.make_individual(0, workloads.full_material(11, 3))] + [workloads.random_robot(1 + i, (6, 6, 6), 50 + i) for i in range(8)]
+    paths = []
+    for ind in inds:
+        write_voxelyze_file(sim, Env(), ind, str(tmp_path), "mix")
+        paths.append(str(tmp_path / "voxelyzeFiles" / ("mix--id_%05i.vxa" % ind.id)))
+
+    def engine():
+        eng = eng_mod.Engine(eng_mod.VOXCAD, 0)
+        eng.set_option("tiled", 1); eng.set_option("tiles_per_robot", 0); eng.set_option("wide", 1)     # the engine's own policy
+        eng.add_vxa_files(paths)
+        return eng
+
+    monkeypatch.delenv("VXH_TILE_SCRATCH_LIMIT", raising=False)
+    with engine() as eng:
+        eng.step(10)
+        want = [eng.state(k) for k in range(len(paths))]
+    with engine() as eng:
+        monkeypatch.setenv("VXH_TILE_SCRATCH_LIMIT", "-1")
+        with pytest.raises(eng_mod.VxhError) as err:
+            eng.step(10)
+        assert "scratch" in str(err.value) and "status -5" in str(err.value)          # VXH_ERR_HIP
+        monkeypatch.delenv("VXH_TILE_SCRATCH_LIMIT")
+        eng.reset()
+        eng.step(10)
+        for k in range(len(paths)):
+            assert np.abs(eng.state(k)[:, :8] - want[k][:, :8]).max() < 1e-12, k
+
+
 def test_the_engine_keeps_the_pools_memory_between_batches(golden_dir, monkeypatch):
     """Round 6, found by looping this file on one box: the engine that had refused a launch (the test above), then reset() and stepped, came
     back with the REST state in 3 % of fresh processes -- the first two uploads of the re-uploaded batch (DRobot, DRobotState: the first

@@ -716,7 +716,7 @@ void form_groups(const std::vector<RobotModel>& robots, int variant, const Optio
         std::stable_sort(g.robots.begin(), g.robots.end(), [&](int a, int b) {
             return (double)robots[a].planned_steps * robots[a].nvox > (double)robots[b].planned_steps * robots[b].nvox; });
         g.count = (int)g.robots.size();
-        if (!g.wide)                    // (k_robot_steps; colliding robots only: the others have no broad-phase runs to spread)
+        if (!g.wide)                    // (k_robot_steps; colliding robots only: what differs between robots is contact work and broad-phase runs)
             for (int r : g.robots) if (robots[r].vxa.self_col_enabled) g.order_use = true;
     }
 }

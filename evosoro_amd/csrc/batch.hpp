@@ -73,7 +73,8 @@ struct GroupPlan {
     int wide = 0;                     // 1: k_robot_wide<block, fluid, tabg> (kernels_wide.hpp)
     int two_tiles = 0;                // wide kernel: a second pose tile in LDS (two barriers per step instead of three)
     int count = 0;
-    bool order_use = false;           // short launches are dispatched "robots due for a broad-phase run first" (kernels_fused.hpp fused_dispatch_slot)
+    bool order_use = false;           // short launches are dispatched "robots due for a broad-phase run first" (kernels_fused.hpp fused_dispatch_slot),
+                                      // long ones by measured cost, longest first (dispatch_order.hpp): k_robot_steps groups with colliding robots
     size_t lds = 0;                   // dynamic LDS bytes
     std::vector<int> robots;
 };

@@ -28,7 +28,7 @@ enum RobotFlags { RF_SELF_COL = 1, RF_GRAV = 2, RF_FLOOR = 4, RF_TEMP = 8, RF_ST
                   // _voxcad development (VXS_Voxel.cpp:236-328): any layer present / which ones
                   RF_DEV = 256, RF_DEV_SIZE = 512 /* Initial- or FinalVoxelSize */, RF_DEV_FSIZE = 1024, RF_DEV_FPHASE = 2048, RF_DEV_FTAD = 4096 };
 
-enum { VXH_ORDER_MAX_STEPS = 128,    // launches of at most this many steps are dispatched "robots due for a broad-phase run first" (kernels_fused.hpp)
+enum { VXH_ORDER_MAX_STEPS = 128,    // launches of at most this many steps are dispatched "robots due for a broad-phase run first", longer ones by measured cost (kernels_fused.hpp)
        VXH_ORDER_HORIZON = 32 };     // ... and what a longer launch calls "due" when it leaves the flags for the launch behind it
 enum { VXH_RIMG_CAP = 2048 };        // entries of a saved contact-row image (the LDS pool holds at most 24 KB / 12 B)
 enum { VXH_FUSED_STATIC_LDS = 480 }; // resident kernel (kernels_fused.hpp): upper bound of its static __shared__ variables
@@ -68,7 +68,7 @@ struct DRobotState {          // mutable per robot
     unsigned long long maxvel2_bits;
     int steps, status, cm_init, active, diverged, col_overflow, rebuild_now, rebuilds;
     int rows_img, reb_step;       // resident kernel: DBatch::rimg_* hold the LDS image of this robot's contact rows as the last launch left it;
-                                  // `steps` at the last broad-phase run (the dispatch order of short launches: fused_dispatch_slot)
+                                  // `steps` at the last broad-phase run (the run prediction of the dispatch order: dispatch_order.hpp)
     int col_tiled, ntrace;        // the contact rows were built by the tiled kernel (DBatch::col_code / tile_xh are valid for them) ; points
                                   // of the centre-of-mass trace recorded so far (SS.CMTrace, VX_Sim.cpp:1537-1547)
     double last_trace_time;

@@ -15,6 +15,7 @@
 #include "engine.hpp"
 #include "import.hpp"
 #include "kernels.hpp"
+#include "kernels_order.hpp"
 #include "launch.hpp"
 
 namespace vxh {
@@ -39,6 +40,13 @@ struct Engine::Device {
         unsigned long long* order_bits[2] = {nullptr, nullptr};
         int order_cur = 0;
         bool order_valid = false;
+        // ... and of long ones (dispatch_order.hpp): the permutation k_dispatch_order makes for a launch, and behind it what every workgroup
+        // of the last long launch measured its robot to cost, by list entry.  The ordering kernel and the launches of a group follow each
+        // other on one stream: one buffer.  No long launch yet (a new batch, a reset): no measurement, the list order.
+        int* order_perm = nullptr;
+        bool cost_valid = false;          // a long launch has left cost words
+        bool last_ordered = false;        // (VXH_PROF_ORDER: the last long launch was ordered by cost; its length)
+        long long last_len = 0;
         hipStream_t stream = nullptr;
         hipEvent_t t0 = nullptr, t1 = nullptr;
     };
@@ -203,6 +211,7 @@ struct Engine::Device {
         for (hipStream_t st : group_streams) hipStreamDestroy(st);
         for (hipEvent_t ev : group_events) hipEventDestroy(ev);
     }
+    void report_dispatch_cost();          // VXH_PROF_ORDER=1: what the robots of the last launch of every group cost, on stderr
 #ifdef VXH_PHASE_TIMING
     void report_contact_rows(const std::vector<RobotModel>& robots);      // the developer build's report of a batch (Engine::clear)
     void report_phase_counters();
@@ -295,6 +304,51 @@ void Engine::set_tiling_allowed(bool on)
     if (prepared_ && rounds_done_ > 0) throw std::logic_error("the kernel choice of a batch that has stepped cannot change");
     tiling_allowed_ = on;
     prepared_ = false;
+}
+
+// VXH_PROF_ORDER=1, after every call: the spread of the robots' cost in the last LONG launch of every colliding k_robot_steps group, as the workgroups
+// measured it (constant-rate clock, whole launch incl. broad-phase runs), and what the dispatch order made of it: the CUs take the
+// workgroups in order as they get free, so the launch ends with the largest sum of a CU -- set against the mean sum (no idle CU at
+// all) and against the same hand-out with the true costs known beforehand (what two robots per CU allow at best).
+void Engine::Device::report_dispatch_cost()
+{
+    int khz = 0;
+    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, 0) != hipSuccess || khz <= 0) khz = 100000;
+    const double us_per_tick = 1e3 / (double)khz;
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+        const Group& g = groups[gi];
+        if (!g.order_perm || !g.cost_valid) continue;
+        std::vector<DispatchCost> c(g.count);
+        std::vector<int> perm(g.count);
+        HIP_OK(hipMemcpy(c.data(), order_ws_cost(g.order_perm, g.count), sizeof(DispatchCost) * c.size(), hipMemcpyDeviceToHost));
+        for (int k = 0; k < g.count; ++k) perm[k] = k;
+        if (g.last_ordered) HIP_OK(hipMemcpy(perm.data(), g.order_perm, sizeof(int) * perm.size(), hipMemcpyDeviceToHost));
+        const double steps = (double)std::max<long long>(1, g.last_len);
+        std::vector<double> t(g.count);
+        double sum = 0, sq = 0, mx = 0, mn = DBL_MAX, reb = 0; int n_reb = 0;
+        for (int k = 0; k < g.count; ++k) {
+            t[k] = us_per_tick * (double)c[k].launch_ticks / steps;
+            sum += t[k]; sq += t[k] * t[k]; mx = std::max(mx, t[k]); mn = std::min(mn, t[k]);
+            if (c[k].reb_ticks > 0) { reb += us_per_tick * c[k].reb_ticks; ++n_reb; }
+        }
+        const double mean = sum / g.count, sigma = std::sqrt(std::max(0.0, sq / g.count - mean * mean));
+        // workgroups per CU: what the LDS leaves room for (threads: 2048 per CU)
+        const int per_cu = std::max(1, std::min((int)(160 * 1024 / (g.lds + VXH_FUSED_STATIC_LDS)), 2048 / std::max(1, g.block)));
+        const int slots = std::max(1, n_cu * per_cu);
+        auto hand_out = [&](const std::vector<int>& order) {
+            std::vector<double> load(std::min(slots, g.count), 0.0);
+            for (int k : order) { auto it = std::min_element(load.begin(), load.end()); *it += t[k]; }
+            return *std::max_element(load.begin(), load.end());
+        };
+        std::vector<int> best(perm);
+        std::stable_sort(best.begin(), best.end(), [&](int a, int b) { return t[a] > t[b]; });
+        const double mean_sum = sum / (double)std::min(slots, g.count);
+        std::fprintf(stderr, "dispatch cost: group %zu, k_robot_steps<%d>, %d robots on %d workgroup slots, last long launch %lld steps, order %s\n"
+                     "  us per step per robot: mean %.3f  sigma %.3f (%.1f %%)  min %.3f  max %.3f; broad-phase run %.1f us (mean of %d robots)\n"
+                     "  us per step per slot: largest sum under this order %.3f | mean sum %.3f | largest sum with the true costs known %.3f  -> idle at the end %.1f %% (%.1f %% at best)\n",
+                     gi, g.block, g.count, slots, g.last_len, g.last_ordered ? "by measured cost" : "of the list", mean, sigma, 100 * sigma / mean, mn, mx,
+                     n_reb ? reb / n_reb : 0.0, n_reb, hand_out(perm), mean_sum, hand_out(best), 100 * (hand_out(perm) / mean_sum - 1), 100 * (hand_out(best) / mean_sum - 1));
+    }
 }
 
 #ifdef VXH_PHASE_TIMING
@@ -413,6 +467,7 @@ const OptionDesc option_table[] = {
     {"graph_steps",       &Options::graph_steps,       OptionDesc::INT,  OptionDesc::RANGE, 0, 1e6,    false, true},
     {"shape_descriptors", &Options::shape_descriptors, OptionDesc::FLAG, OptionDesc::WHOLE, 0, 1,      false, false},      // (robots added FROM NOW ON carry the surface mesh)
     {"host_results",      &Options::host_results,      OptionDesc::FLAG, OptionDesc::ANY,   0, 0,      false, false},
+    {"dispatch_order",    &Options::dispatch_order,    OptionDesc::FLAG, OptionDesc::WHOLE, 0, 1,      false, false},
 };
 const OptionDesc& find_option(const std::string& key)
 {
@@ -598,7 +653,13 @@ void Engine::prepare()
         D.groups.emplace_back(std::move(P.groups[gi]));
         Device::Group& g = D.groups.back();
         g.list = D.upload(g.robots);
-        if (g.order_use) for (int k = 0; k < 2; ++k) g.order_bits[k] = D.alloc_zero<unsigned long long>((size_t)(g.count + 63) / 64 + 1);
+        if (g.order_use) {
+            for (int k = 0; k < 2; ++k) g.order_bits[k] = D.alloc_zero<unsigned long long>((size_t)(g.count + 63) / 64 + 1);
+            g.order_perm = (int*)D.alloc_zero<unsigned long long>((size_t)order_ws_words(g.count));
+            // the ordering kernel once, here: its first launch loads its code, 0.4 ms that would otherwise fall into the first long call
+            hipLaunchKernelGGL(k_dispatch_order, dim3((g.count + VXH_ORDER_BLOCK - 1) / VXH_ORDER_BLOCK), dim3(VXH_ORDER_BLOCK), 0, D.stream,
+                               order_ws_cost(g.order_perm, g.count), g.count, 0, g.order_perm);
+        }
         D.give_stream(g, gi);
     }
     D.reb_blocks = (int)P.reb_robot.size();
@@ -629,11 +690,11 @@ void Engine::reset() { if (!robots_.empty()) prepare(); }
 
 // (which kernel variant takes a robot -- fused_variant, wide_listed, resident_block -- is decided in batch.cpp; a Group carries the answer)
 static void launch_group(const DBatch& B, int block, bool fluid, bool tabg, bool wide, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters, int two_tiles = 0,
-                         const unsigned long long* order_in = nullptr, unsigned long long* order_out = nullptr)
+                         const unsigned long long* order_in = nullptr, unsigned long long* order_out = nullptr, bool cost = false)
 {
     if (wide) { launch_wide_group(B, fluid, tabg, list, count, lds, s, cap, iters, two_tiles); return; }
-    if (fluid) launch_fused_mesh(B, block, tabg, list, count, lds, s, cap, iters, order_in, order_out);
-    else launch_fused_land(B, block, tabg, list, count, lds, s, cap, iters, order_in, order_out);
+    if (fluid) launch_fused_mesh(B, block, tabg, list, count, lds, s, cap, iters, order_in, order_out, cost);
+    else launch_fused_land(B, block, tabg, list, count, lds, s, cap, iters, order_in, order_out, cost);
 }
 
 // A call in two halves: advance_launch enqueues every kernel of the call and returns; advance_finish waits for the device, reads
@@ -712,6 +773,7 @@ void Engine::advance_launch(long long max_rounds)
     // mapped host memory -- which is more than the launch gained.  Polling the last event instead of sleeping on the stream: no gain.)
     if (fused) {
         const int iters = std::max(1, opt_.steps_per_launch);
+        const bool prof_order = std::getenv("VXH_PROF_ORDER") != nullptr;      // (the spread under the list order too: dispatch_order = 0)
         for (auto& g : D.groups) {
             if (single) break;               // (its span is the call's: ev0 .. ev1; every event record is a packet the command processor works through)
             HIP_OK(hipStreamWaitEvent(g.stream, D.ev0, 0));
@@ -720,11 +782,24 @@ void Engine::advance_launch(long long max_rounds)
         for (long long done = 0; done < todo || done == 0; done += iters) {
             for (size_t k = 0; k < D.groups.size(); ++k) {
                 auto& g = D.groups[k];
-                // a short launch (what is left of the call, or the launch length itself): flagged robots first, flags for the next one
+                // A short launch (what is left of the call, or the launch length itself): flagged robots first, flags for the next one.  A long
+                // one: the robots by what they are expected to cost in it, longest first, from what the last long launch measured -- the
+                // kernel instances that measure (COST), with k_dispatch_order in front (length 0: all keys equal, the list order).
                 const long long len = std::min<long long>(iters, std::max<long long>(1, todo - done));
-                const bool dyn = g.order_use && g.order_valid && len <= VXH_ORDER_MAX_STEPS;
-                launch_group(B, g.block, g.fluid != 0, g.tabg != 0, g.wide != 0, g.list, g.count, g.lds, single ? D.stream : g.stream, cap, iters, g.two_tiles,
-                             dyn ? g.order_bits[g.order_cur] : nullptr, g.order_use ? g.order_bits[g.order_cur ^ 1] : nullptr);
+                const bool is_short = len <= VXH_ORDER_MAX_STEPS;
+                const bool measure = g.order_use && !is_short && (opt_.dispatch_order != 0 || prof_order);
+                const bool dyn = g.order_use && g.order_valid && is_short && opt_.dispatch_order != 0;
+                hipStream_t st = single ? D.stream : g.stream;
+                const unsigned long long* order_in = dyn ? g.order_bits[g.order_cur] : nullptr;
+                if (measure) {
+                    const bool by_cost = g.cost_valid && opt_.dispatch_order != 0;
+                    hipLaunchKernelGGL(k_dispatch_order, dim3((g.count + VXH_ORDER_BLOCK - 1) / VXH_ORDER_BLOCK), dim3(VXH_ORDER_BLOCK), 0, st,
+                                       order_ws_cost(g.order_perm, g.count), g.count, by_cost ? (int)len : 0, g.order_perm);
+                    order_in = (const unsigned long long*)g.order_perm;
+                    g.cost_valid = true; g.last_ordered = by_cost; g.last_len = len;
+                }
+                launch_group(B, g.block, g.fluid != 0, g.tabg != 0, g.wide != 0, g.list, g.count, g.lds, st, cap, iters, g.two_tiles, order_in,
+                             g.order_use ? g.order_bits[g.order_cur ^ 1] : nullptr, measure);
                 if (g.order_use) { g.order_cur ^= 1; g.order_valid = true; }      // (every launch leaves the flags for the next)
                 ++launches; ++group_launches[k];
             }
@@ -813,6 +888,7 @@ void Engine::advance_finish()
     hs.mark("wait for the GPU");
     download_control(true);
     hs.mark("control blocks back");
+    if (P.fused && std::getenv("VXH_PROF_ORDER")) D.report_dispatch_cost();
     // dominant kernel of this call (batch.cpp decides which unit; here: the pair of events that timed it)
     std::vector<int>& steps = P.steps_before;                  // (from here on: the steps this call took)
     for (size_t r = 0; r < robots_.size(); ++r) steps[r] = host_[r].steps - steps[r];

@@ -49,6 +49,7 @@ struct Options {
     int shape_descriptors = 0;                 // _voxcad robots added from now on carry the deformable surface mesh (voxelyze --computeShapeDescriptors): they are
                                                // stepped by the MESH kernel variants, which record the directional strains the final mesh needs
     int host_results = 0;                      // every result from the downloaded voxel state on the host (cross-check)
+    int dispatch_order = 1;                    // resident kernel: the workgroups of a launch by measured cost, longest first (dispatch_order.hpp); 0: the list order
 };
 
 class Engine {

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_types.hpp"
+#include "dispatch_order.hpp"
 
 namespace vxh {
 

@@ -29,6 +29,7 @@
 //   st   [6][BLOCK]        MESH, BLOCK <= 512: directional strains of the previous step (DBatch::strain otherwise)
 //   mesh [3][nmv]          MESH only: vertices of the drag mesh (robots in a fluid)
 #pragma once
+#include <type_traits>
 
 namespace vxh {
 
@@ -893,6 +894,14 @@ __device__ __forceinline__ void fused_horizon_decide(const DRobot& R, DRobotStat
     if (rebuild) K.flags = in.flags | 8;
 }
 
+// Dispatch order of LONG launches (more than VXH_ORDER_MAX_STEPS steps; dispatch_order.hpp): a launch ends with its slowest CU, and a CU steps its
+// robots one after the other, so the workgroups are handed out by descending expected cost -- the permutation k_dispatch_order (kernels_order.hpp,
+// queued in front of the launch) leaves in the group's workspace.  The cost is measured by the COST instances of k_robot_steps, which step the
+// long launches of colliding groups: one lane reads the constant-rate clock in front of and behind the step loop and brackets the broad-phase
+// runs, and the workgroup leaves the result for its robot in the workspace (by list entry).  The start values live in static LDS: a scalar
+// register held across the step loop costs the loop a spill.  Short launches, and groups without collisions, run the instances without any of
+// it (DESIGN.md "The cost of a launch": the numbers).
+//
 // Dispatch order of SHORT launches (a call of a few dozen steps: one launch, two robots per CU one after the other).  A broad-phase run
 // is ~42 us, a sixth of a 20-step launch, and the launch ends with its slowest CU: with the robots in their fixed list order the last
 // workgroups to be dispatched -- which land on the CUs that a run has already delayed -- bring runs of their own four times out of five
@@ -918,7 +927,14 @@ __device__ __forceinline__ int fused_dispatch_slot(const unsigned long long* __r
     return i;      // (not reached: flagged + unflagged == count)
 }
 
-template <int BLOCK, int NACC, bool MESH, bool TABG>
+// static LDS of the COST instances: the constant-rate clock in front of the step loop / at the start of the broad-phase run in progress, ticks
+// in broad-phase runs during this launch / in the last one
+struct FusedCostLds { unsigned long long t0, treb; unsigned reb_sum, reb_last; };
+struct FusedNoLds {};
+
+// order_in / order_out.  Not COST: the flag words a short launch reads (null: the list order) / those every launch leaves for the next.
+// COST: order_in is the launch's permutation (never null) with the cost words behind it (dispatch_order.hpp order_ws_cost).
+template <int BLOCK, int NACC, bool MESH, bool TABG, bool COST>
 __global__ __launch_bounds__(BLOCK, (BLOCK + 255) / 256) void k_robot_steps(DBatch B, const DRobot* __restrict__ robots,
                                                                             const int* __restrict__ robot_list, long long step_cap, int iters,
                                                                             int lds_doubles, const unsigned long long* __restrict__ order_in,
@@ -940,20 +956,23 @@ __global__ __launch_bounds__(BLOCK, (BLOCK + 255) / 256) void k_robot_steps(DBat
     // which needs every voxel's new velocity, stays between the barriers
     __shared__ FusedCtl s_ctl[2];
     __shared__ int s_div, s_na[3], s_seg[2 * (BLOCK / 64)];
-    static_assert(sizeof(DRobotState) + 2 * sizeof(FusedCtl) + 5 * sizeof(int) + 2 * 16 * sizeof(int) + 16 <= VXH_FUSED_STATIC_LDS, "static LDS bound");
+    __shared__ std::conditional_t<COST, FusedCostLds, FusedNoLds> s_cost;
+    static_assert(sizeof(DRobotState) + 2 * sizeof(FusedCtl) + 5 * sizeof(int) + 2 * 16 * sizeof(int) + sizeof(FusedCostLds) + 16 <= VXH_FUSED_STATIC_LDS, "static LDS bound");
 
     const int tid = threadIdx.x;
 #ifdef VXH_PHASE_TIMING
     const unsigned long long t_entry = __builtin_readcyclecounter();
 #endif
-    const int slot = order_in ? __builtin_amdgcn_readfirstlane(fused_dispatch_slot(order_in, (int)gridDim.x, (int)blockIdx.x)) : (int)blockIdx.x;
+    int slot;
+    if constexpr (COST) slot = __builtin_amdgcn_readfirstlane(((const int*)order_in)[blockIdx.x]);
+    else slot = order_in ? __builtin_amdgcn_readfirstlane(fused_dispatch_slot(order_in, (int)gridDim.x, (int)blockIdx.x)) : (int)blockIdx.x;
     const int r = __builtin_amdgcn_readfirstlane(robot_list[slot]);   // robots of one launch group, longest-running first; uniform -> scalar loads of R
     const DRobot& R = robots[r];            // separate noalias argument: its loads stay scalar although the kernel stores to HBM
     const unsigned nv = B.nv;
     const int base = R.vox_begin;
     const bool valid = tid < R.nvox;
     const int v = base + tid;
-    if (tid == 0) { rs = B.rstate[r]; s_na[0] = s_na[1] = s_na[2] = 0; }
+    if (tid == 0) { rs = B.rstate[r]; s_na[0] = s_na[1] = s_na[2] = 0; if constexpr (COST) s_cost.reb_sum = s_cost.reb_last = 0u; }
     // the robot's class tables: copied into LDS, or (TABG: robots with per-voxel evolved stiffness, where nearly every
     // bond and voxel is a class of its own and the tables outgrow the LDS) read from HBM / L2 where they lie
     const int nbd = TABG ? 0 : R.n_bclass * (int)(sizeof(DBondClass) / 8), nvd = TABG ? 0 : R.n_vclass * (int)(sizeof(DVoxClass) / 8);
@@ -1133,6 +1152,8 @@ __global__ __launch_bounds__(BLOCK, (BLOCK + 255) / 256) void k_robot_steps(DBat
     unsigned long long reb_cycles = 0;
     if (!MESH && B.prof && (tid & 63) == 0) atomicAdd(&B.prof[(tid >> 6) * 8 + 6], __builtin_readcyclecounter() - t_entry);   // prologue
 #endif
+    // (the clock is read here, behind the prologue's loads: the instruction waits for every scalar load and LDS access in flight)
+    if constexpr (COST) { if (tid == 0) s_cost.t0 = __builtin_amdgcn_s_memrealtime(); }
     int it = 0;
     for (;; ++it) {
         const FusedCtl& K = s_ctl[it & 1];
@@ -1154,6 +1175,7 @@ __global__ __launch_bounds__(BLOCK, (BLOCK + 255) / 256) void k_robot_steps(DBat
         const unsigned long long t_reb0 = __builtin_readcyclecounter();
 #endif
         if (__builtin_expect(k_rebuild, 0)) {
+            if constexpr (COST) { if (tid == 0) s_cost.treb = __builtin_amdgcn_s_memrealtime(); }
             fused_rebuild<BLOCK>(B, R, rs, ps, acc, NACC * 6 * BLOCK, (double*)cmask, max(0, lds_doubles - (int)((double*)cmask - lds)), vct);
 #ifdef VXH_PHASE_TIMING
             if (VXH_DBG(16) && B.prof) {     // cross-check: the plain scan must leave the same rows (count, partners, stiffness bits)
@@ -1184,6 +1206,7 @@ __global__ __launch_bounds__(BLOCK, (BLOCK + 255) / 256) void k_robot_steps(DBat
 #pragma unroll
             for (int k = 1; k < NACC * 6; ++k) acc[k * BLOCK + tid] = 0.0;      // the scratch of the broad-phase (plane 0: below)
             scratch_used = true;
+            if constexpr (COST) { if (tid == 0) { const unsigned dtr = (unsigned)(__builtin_amdgcn_s_memrealtime() - s_cost.treb); s_cost.reb_last = dtr; s_cost.reb_sum += dtr; } }
         }
 #ifdef VXH_PHASE_TIMING
         // developer build: broad-phase runs (incl. the copy of the rows) and their cycles, wave 0 of every workgroup; the largest
@@ -1334,17 +1357,42 @@ __global__ __launch_bounds__(BLOCK, (BLOCK + 255) / 256) void k_robot_steps(DBat
         if (entry[a] != -1) B.small_angle[(unsigned)a * nv + (base + (entry[a] & 1023))] = (unsigned char)((modebits >> (2 * a)) & 3u);
     if (tid == 0) {
         B.rstate[r] = rs; if (B.rstate_mirror) B.rstate_mirror[r] = rs;
+        // (the list entry is worked out again rather than kept: a scalar register held across the step loop costs the loop a spill)
+        if constexpr (COST) {      // what this launch cost, and what the next long one's order needs of the robot's state (dispatch_order.hpp)
+            const bool horizon = (R.flags & RF_SELF_COL) && (R.flags & RF_HORIZON_COL);
+            DispatchCost& mine = order_ws_cost((const int*)order_in, (int)gridDim.x)[((const int*)order_in)[blockIdx.x]];
+            DispatchCost c = {0.f, 0.f, 0.f, 0.f, 0, 0};
+            const unsigned in_runs = horizon ? s_cost.reb_sum : 0u;      // (a robot that runs the broad-phase every step: the runs are part of its step)
+            const long long ticks = (long long)(__builtin_amdgcn_s_memrealtime() - s_cost.t0);
+            c.launch_ticks = (int)ticks;
+            c.step_ticks = it > 0 ? (float)(ticks - (long long)in_runs) / (float)it : mine.step_ticks;      // (a launch without a step measures nothing)
+            c.reb_ticks = !horizon ? 0.f : (s_cost.reb_last ? (float)s_cost.reb_last : mine.reb_ticks);      // (no run in this launch: what an earlier one took)
+            if (rs.status == 0) {
+                // steps until the robot's own stop condition (step_control_begin); none: as good as unbounded
+                double left = 1e9;
+                if (R.stop_type == 1) left = (double)((int)(R.stop_value + 0.5) + 1 - rs.steps);
+                else if (R.stop_type == 2) left = (R.stop_value + R.afterlife - rs.cur_time) / R.dt + 1.0;
+                else if (R.stop_type == 3) left = (R.temp_period_d * R.stop_value - rs.cur_time) / R.dt + 1.0;
+                c.left = (int)fmin(fmax(left, 1.0), 1e9);
+                if (horizon) {     // the next run: the displacement since the last one, growing at the average rate since then
+                    const double thr = (R.col_horizon - 1.0) / 2;
+                    if (thr > 0) { c.disp_frac = (float)(rs.max_disp / thr); c.rate_frac = (float)(rs.max_disp / (double)max(1, rs.steps - rs.reb_step) / thr); }
+                }
+            }
+            mine = c;
+        }
         if (order_out) {       // due for a broad-phase run within a launch like this one?  (see fused_dispatch_slot)
             bool soon = false;
             if (rs.status == 0 && (R.flags & RF_SELF_COL) && (R.flags & RF_HORIZON_COL)) {
                 const double rate = rs.max_disp / (double)max(1, rs.steps - rs.reb_step);
-                // (`it`: the steps of this launch; a long launch -- whose own order does not matter -- leaves the flags for a short one behind it.
+                // (`it`: the steps of this launch; a long launch -- whose own order is by cost -- leaves the flags for a short one behind it.
                 // Generous: a robot flagged for nothing costs nothing, a run in the second round of a late CU costs the launch 42 us; 2.5 against
                 // 1.25 launch lengths: the driver's command 1.383-1.405e10 against 1.380-1.403e10, same box, alternating)
                 soon = rs.max_disp + rate * (2.5 * (double)min(max(1, it), (int)VXH_ORDER_HORIZON)) > (R.col_horizon - 1.0) / 2;
             }
-            // (the slot is worked out again rather than kept: a scalar register held across the step loop costs the loop a spill)
-            const int my = order_in ? fused_dispatch_slot(order_in, (int)gridDim.x, (int)blockIdx.x) : (int)blockIdx.x;
+            int my;
+            if constexpr (COST) my = ((const int*)order_in)[blockIdx.x];
+            else my = order_in ? fused_dispatch_slot(order_in, (int)gridDim.x, (int)blockIdx.x) : (int)blockIdx.x;
             const unsigned long long bit = 1ull << (my & 63);
             if (soon) atomicOr(&order_out[my >> 6], bit); else atomicAnd(&order_out[my >> 6], ~bit);
         }

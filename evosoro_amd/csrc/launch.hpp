@@ -7,6 +7,7 @@
 #include <stdexcept>
 #include <string>
 #include "device_types.hpp"
+#include "dispatch_order.hpp"
 
 namespace vxh {
 
@@ -29,11 +30,12 @@ inline void grant_dynamic_lds(const void* kernel, size_t (&granted)[64], size_t 
     }
 }
 
-// k_robot_steps<block, nacc, FLUID, TABG> (kernels_fused.hpp): block in {256, 512, 768, 1024}; land robots / land_water robots
+// k_robot_steps<block, nacc, FLUID, TABG, COST> (kernels_fused.hpp): block in {256, 512, 768, 1024}; land robots / land_water robots;
+// cost: the instances that measure what their robots cost (order_in: the launch's permutation with the cost words behind it, never null)
 void launch_fused_land(const DBatch& B, int block, bool tabg, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters,
-                       const unsigned long long* order_in, unsigned long long* order_out);
+                       const unsigned long long* order_in, unsigned long long* order_out, bool cost);
 void launch_fused_mesh(const DBatch& B, int block, bool tabg, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters,
-                       const unsigned long long* order_in, unsigned long long* order_out);
+                       const unsigned long long* order_in, unsigned long long* order_out, bool cost);
 // k_robot_wide<512, MESH, TABG> (kernels_wide.hpp)
 void launch_wide_group(const DBatch& B, bool mesh, bool tabg, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters, int two_tiles);
 // k_tile_steps<TABG, MESH, FLUID> (kernels_tiled.hpp); mesh_kind: 0 = _voxcad, 1 = land_water robot on land, 2 = in a fluid

@@ -246,7 +246,11 @@ int  vxh_count_bond_modes(const vxh_engine* e, long long* large_angle_out, long 
  *                       by the kernel variants that record the directional strains the deformed mesh needs): vxh_get_mesh /
  *                       vxh_get_shape_descriptors then answer for them -- `voxelyze --computeShapeDescriptors`.  Default 0.
  *   "host_results"      1 = vxh_get_result evaluates every tag on the host from the downloaded voxel state instead of from the
- *                       device-side reductions (cross-checks; the numbers are the same) */
+ *                       device-side reductions (cross-checks; the numbers are the same)
+ *   "dispatch_order"    1 (default) = the workgroups of a resident-kernel launch of more than 128 steps take the robots by what the
+ *                       previous launch measured them to cost, longest first, so that the CUs finish together (shorter launches: the
+ *                       robots due for a collision broad-phase run first); 0 = in the order of the host's list (A/B runs, tests).
+ *                       The robots do not interact: the same results, bit for bit, either way.  May be changed at any time. */
 int  vxh_set_option(vxh_engine* e, const char* key, double value);
 
 const char* vxh_strerror(int status);

@@ -3,6 +3,14 @@
 
 namespace vxh {
 
+// angle constants of Vec3D.h / VX_Bond.h (the kernels' small-angle logic: kernels_math.hpp; the host derives DBatch::small_angle_w etc. from them)
+#define VXH_PI 3.14159265358979
+#define VXH_DISCARD_ANGLE_RAD 1e-7
+#define VXH_SMALL_ANGLE_RAD 1.732e-2
+#define VXH_SA_BOND_BEND_RAD 0.05
+#define VXH_SA_BOND_EXT_PERC 1.30
+#define VXH_HYST 1.1
+
 // per-class constant tables: a handful of entries for a whole population (all robots of an evosoro run share
 // one palette), read through the scalar/L1 caches instead of streaming ~170 B of constants per bond
 struct DVoxClass {
@@ -150,6 +158,35 @@ struct DResult {
 
 // (collision partners per surface voxel: DRobot::col_cap; a row that would need more -> VXH_ROBOT_COL_OVERFLOW)
 
+// The words of DBatch::prof (developer builds, -DVXH_PHASE_TIMING): written by the kernels' timer macros and cross-checks (kernels_group.hpp,
+// kernels_dev.hpp, kernels_tiled.hpp), read back by dev_report.cpp.  Three blocks and a run of single counters; the single counters lie
+// inside the timeline block, in the words of tiles 246 and up, which a timeline run (VXH_PROF_TILES) of that many tiles overwrites.
+enum ProfSlot {
+    VXH_PROF_WAVE = 0,                // [16 wavefronts][8] cycle sums of the phases of a step: wavefront * 8 + phase.  Resident / wide: phases 0..5, then
+                                      // 6 / 7 = prologue / epilogue of the kernel (MESH: mesh vertices / facets of the drag); tiled: eight phases
+    VXH_PROF_WAVE_WORDS = 8,
+    VXH_PROF_BARRIER_POLLS = 120, VXH_PROF_BARRIERS, VXH_PROF_BARRIER_CYCLES,   // robot barrier of the tiled kernel (in the block of a 16th wavefront, which no kernel has)
+    VXH_PROF_TILE = 128,              // [256 tiles][8] timeline of one step of the first tiles (real-time counter): VXH_PROF_TILE + tile * 8 + mark
+    VXH_PROF_TILE_WORDS = 8, VXH_PROF_TILE_COUNT = 256,
+    VXH_PROF_WORDS = 16 * 8 + 256 * 8,  // size of the array
+    // broad-phase run of the resident kernel, cycle sums of the first thread: staging | its own scan | wait for the slowest wavefront
+    VXH_PROF_REB_STAGE = 2100, VXH_PROF_REB_SCAN, VXH_PROF_REB_WAIT,
+    VXH_PROF_PRO_TABLES = 2103,       // prologue of the resident kernel: tables -> LDS, first barrier
+    VXH_PROF_XREB_ROWS = 2104, VXH_PROF_XREB_DIFFER,   // dbg 16, plain scan against bit-matrix scan: rows built by both | rows that differ
+    VXH_PROF_PRO_STATE = 2106,        // prologue: state load, zeroing, first control
+    VXH_PROF_REB_LAUNCHES = 2107,     // workgroup-launches with at least one broad-phase run
+    VXH_PROF_REB_RUNS = 2108, VXH_PROF_REB_CYCLES, VXH_PROF_REB_MAX_CYCLES,   // runs | their cycles | most cycles of one workgroup in one launch
+    VXH_PROF_XROW_AS_MANY = 2111,     // dbg 8, differing lanes with as many mask bits as pairs in reach
+    VXH_PROF_PRO_R2L = 2113,          // prologue: rows_to_lds as a whole ...
+    VXH_PROF_R2L_COUNT = 2114, VXH_PROF_R2L_SCAN, VXH_PROF_R2L_COPY,   // ... and its parts (incl. the calls after broad-phase runs)
+    VXH_PROF_XROW_LDS_DIFFERS = 2117, VXH_PROF_XROW_FEWER, VXH_PROF_XROW_MORE,   // dbg 8: LDS row differs from memory | fewer / more mask bits than pairs in reach
+    VXH_PROF_XREB_LONGER = 2120, VXH_PROF_XREB_SHORTER, VXH_PROF_XREB_MAX_NEW, VXH_PROF_XREB_MAX_OLD, VXH_PROF_XREB_SUM_NEW, VXH_PROF_XREB_SUM_OLD,   // dbg 16
+    VXH_PROF_REB_ROWS = 2126,         // broad-phase run: bit matrix -> rows
+    VXH_PROF_XROW_LANES = 2127, VXH_PROF_XROW_DIFFER,   // dbg 8, LDS rows against memory rows: lanes checked | lanes with different bits
+    VXH_PROF_DRAG = 2130,             // [5] facet pass of the drag (fused_drag)
+    VXH_PROF_TILE_VOXEL = 2140        // [4] voxel phase of the tiled kernel
+};
+
 // all device pointers of a batch; passed to kernels by value
 struct DBatch {
     int n_robots, nv;                 // nv = total padded voxel slots (multiple of 64 per robot)
@@ -205,7 +242,7 @@ struct DBatch {
     // round trip of coalesced loads instead of ordinal -> count -> scan -> rows, three dependent round trips and three barriers
     int* rimg_code; double* rimg_a1; int* rimg_seg; int* rimg_rowd;     // [n_img * VXH_RIMG_CAP] x 2, [n_img * 64], [nv]
     int col_rows, pad2;               // total surface voxels of colliding robots
-    int* col_partner;                 // per robot a block [col_cap][nsurf] (partner-major; kernels.hpp col_at) of global voxel slots
+    int* col_partner;                 // per robot a block [col_cap][nsurf] (partner-major; kernels_physics.hpp col_at) of global voxel slots
     double* col_a1;                   // same shape: linear stiffness a1 of that collision bond
     // land_water fluid drag (LW/VX_Sim.cpp:1516-1597): deformable surface mesh of every fluid robot
     int total_mv, pad3;               // mesh vertices of all fluid robots
@@ -260,7 +297,7 @@ struct DBatch {
     int* tile_xh;                     // [total tiles][VXH_TILE_XH] contact partners owned by other tiles that the tile mirrors (global slots)
     int* tile_xhn;                    // [total tiles] their number
     double* trace;                    // centre-of-mass traces: 4 doubles (time, x, y, z) per entry, robots one after the other (DRobot::trace_begin)
-    unsigned long long* prof;         // developer builds (-DVXH_PHASE_TIMING): per-wave phase cycle sums, else null
+    unsigned long long* prof;         // developer builds (-DVXH_PHASE_TIMING): [VXH_PROF_WORDS] counters (ProfSlot above), else null
     // constants from Vec3D.h evaluated by the host libm (thresholds of the small-angle logic)
     double small_angle_w, smallish_angle_w, slthresh_acos2sqrt;
 };

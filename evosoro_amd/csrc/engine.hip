@@ -14,8 +14,8 @@
 #include "batch.hpp"
 #include "engine.hpp"
 #include "import.hpp"
-#include "kernels.hpp"
-#include "kernels_order.hpp"
+#include "dev_report.hpp"
+#include "device_types.hpp"
 #include "launch.hpp"
 
 namespace vxh {
@@ -306,15 +306,11 @@ void Engine::set_tiling_allowed(bool on)
     prepared_ = false;
 }
 
-// VXH_PROF_ORDER=1, after every call: the spread of the robots' cost in the last LONG launch of every colliding k_robot_steps group, as the workgroups
-// measured it (constant-rate clock, whole launch incl. broad-phase runs), and what the dispatch order made of it: the CUs take the
-// workgroups in order as they get free, so the launch ends with the largest sum of a CU -- set against the mean sum (no idle CU at
-// all) and against the same hand-out with the true costs known beforehand (what two robots per CU allow at best).
+// VXH_PROF_ORDER=1, after every call: what the robots cost in the last LONG launch of every colliding k_robot_steps group (dev_report.cpp)
 void Engine::Device::report_dispatch_cost()
 {
     int khz = 0;
     if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, 0) != hipSuccess || khz <= 0) khz = 100000;
-    const double us_per_tick = 1e3 / (double)khz;
     for (size_t gi = 0; gi < groups.size(); ++gi) {
         const Group& g = groups[gi];
         if (!g.order_perm || !g.cost_valid) continue;
@@ -323,100 +319,27 @@ void Engine::Device::report_dispatch_cost()
         HIP_OK(hipMemcpy(c.data(), order_ws_cost(g.order_perm, g.count), sizeof(DispatchCost) * c.size(), hipMemcpyDeviceToHost));
         for (int k = 0; k < g.count; ++k) perm[k] = k;
         if (g.last_ordered) HIP_OK(hipMemcpy(perm.data(), g.order_perm, sizeof(int) * perm.size(), hipMemcpyDeviceToHost));
-        const double steps = (double)std::max<long long>(1, g.last_len);
-        std::vector<double> t(g.count);
-        double sum = 0, sq = 0, mx = 0, mn = DBL_MAX, reb = 0; int n_reb = 0;
-        for (int k = 0; k < g.count; ++k) {
-            t[k] = us_per_tick * (double)c[k].launch_ticks / steps;
-            sum += t[k]; sq += t[k] * t[k]; mx = std::max(mx, t[k]); mn = std::min(mn, t[k]);
-            if (c[k].reb_ticks > 0) { reb += us_per_tick * c[k].reb_ticks; ++n_reb; }
-        }
-        const double mean = sum / g.count, sigma = std::sqrt(std::max(0.0, sq / g.count - mean * mean));
-        // workgroups per CU: what the LDS leaves room for (threads: 2048 per CU)
-        const int per_cu = std::max(1, std::min((int)(160 * 1024 / (g.lds + VXH_FUSED_STATIC_LDS)), 2048 / std::max(1, g.block)));
-        const int slots = std::max(1, n_cu * per_cu);
-        auto hand_out = [&](const std::vector<int>& order) {
-            std::vector<double> load(std::min(slots, g.count), 0.0);
-            for (int k : order) { auto it = std::min_element(load.begin(), load.end()); *it += t[k]; }
-            return *std::max_element(load.begin(), load.end());
-        };
-        std::vector<int> best(perm);
-        std::stable_sort(best.begin(), best.end(), [&](int a, int b) { return t[a] > t[b]; });
-        const double mean_sum = sum / (double)std::min(slots, g.count);
-        std::fprintf(stderr, "dispatch cost: group %zu, k_robot_steps<%d>, %d robots on %d workgroup slots, last long launch %lld steps, order %s\n"
-                     "  us per step per robot: mean %.3f  sigma %.3f (%.1f %%)  min %.3f  max %.3f; broad-phase run %.1f us (mean of %d robots)\n"
-                     "  us per step per slot: largest sum under this order %.3f | mean sum %.3f | largest sum with the true costs known %.3f  -> idle at the end %.1f %% (%.1f %% at best)\n",
-                     gi, g.block, g.count, slots, g.last_len, g.last_ordered ? "by measured cost" : "of the list", mean, sigma, 100 * sigma / mean, mn, mx,
-                     n_reb ? reb / n_reb : 0.0, n_reb, hand_out(perm), mean_sum, hand_out(best), 100 * (hand_out(perm) / mean_sum - 1), 100 * (hand_out(best) / mean_sum - 1));
+        vxh::report_dispatch_cost(gi, c, perm, g.block, g.lds, g.last_len, g.last_ordered, n_cu, 1e3 / (double)khz);
     }
 }
 
 #ifdef VXH_PHASE_TIMING
-// The developer build's report of a batch that is about to go (scripts/dev_gpu_diag.py and scripts/tile_timeline_sum.py parse it)
+// The developer build's report of a batch that is about to go (dev_report.cpp)
 void Engine::Device::report_contact_rows(const std::vector<RobotModel>& robots)
 {
     if (!std::getenv("VXH_COL_STATS") || B.col_rows <= 0) return;    // lengths of the contact rows as the last broad-phase runs left them
-    std::vector<int> cnt(B.col_rows);
+    std::vector<int> cnt(B.col_rows), nsurf;
     HIP_OK(hipMemcpy(cnt.data(), B.col_cnt, sizeof(int) * cnt.size(), hipMemcpyDeviceToHost));
-    long long hist[9] = {0}, total = 0; int mx = 0;
-    for (int c : cnt) { total += c; mx = std::max(mx, c); ++hist[c == 0 ? 0 : std::min(8, 1 + (c - 1) / 8)]; }
-    fprintf(stderr, "contact rows: %zu surface voxels, %.1f partners on average, longest %d; rows by length 0 | 1-8 | 9-16 | ... | 57-64:", cnt.size(), (double)total / cnt.size(), mx);
-    for (long long v : hist) fprintf(stderr, " %lld", v);
-    long long per_robot_max = 0;
-    for (size_t r = 0; r < robots.size(); ++r) {
-        long long sum = 0;
-        const int b = surf_begin[r], n = robots[r].nsurf;
-        for (int i = 0; i < n; ++i) sum += cnt[b + i];
-        per_robot_max = std::max(per_robot_max, sum);
-    }
-    fprintf(stderr, "\n  most partners in one robot: %lld\n", per_robot_max);
+    for (const RobotModel& m : robots) nsurf.push_back(m.nsurf);
+    vxh::report_contact_rows(cnt, surf_begin, nsurf);
 }
 
 void Engine::Device::report_phase_counters()
 {
     if (!B.prof) return;
-    unsigned long long h[16 * 8 + 256 * 8];
-    HIP_OK(hipMemcpy(h, B.prof, sizeof(h), hipMemcpyDeviceToHost));
-    if (std::getenv("VXH_PROF_TILES")) {    // the first tiles at one step of the last launch: real-time counter (10 ns ticks) at the step's boundaries
-        unsigned long long t0 = ~0ull;
-        for (int t = 0; t < std::min(256, B.n_tiles); ++t) if (h[128 + t * 8]) t0 = std::min(t0, h[128 + t * 8]);
-        fprintf(stderr, "tile: top  halo-done  bond-done  voxel-done  C-passed | svc: barrier-resolved | next top | mv-published   (us after the first tile's top)\n");
-        for (int t = 0; t < std::min(256, B.n_tiles); ++t) {
-            fprintf(stderr, "tile %3d:", t);
-            for (int k : {0, 1, 2, 3, 4, 5, 6, 7}) fprintf(stderr, " %7.2f", 0.01 * (double)(long long)(h[128 + t * 8 + k] - t0));
-            fprintf(stderr, "\n");
-        }
-    }
-    if (h[2112]) fprintf(stderr, "contact rows in LDS: %llu wavefront copies, %llu did not fit (mean capacity %.0f pairs); cross-check (dbg 8): %llu lanes, %llu with different bits, %llu whose LDS row differs from memory; of the differing lanes: %llu with fewer mask bits than pairs in reach, %llu with more, %llu with as many\n",
-                        h[2112], h[2113], h[2114] ? (double)h[2114] * 12.0 / (double)h[2112] : 0.0, h[2115], h[2116], h[2117], h[2118], h[2119], h[2111]);
-    if (h[2108]) fprintf(stderr, "broad-phase runs (resident kernel, with the copy of the rows): %llu, %.0f cycles each on average; workgroup-launches with at least one: %llu; "
-                        "most cycles one workgroup spent in them in one launch (maximum over ALL launches): %llu\n", h[2108], (double)h[2109] / (double)h[2108], h[2107], h[2110]);
-    if (h[2108] && h[2100]) fprintf(stderr, "   of a broad-phase run, cycles on average (first wavefront): staging the surface list %.0f | its own scan / block pairs %.0f | wait for the "
-                                  "slowest wavefront %.0f | bit matrix -> rows %.0f | the rest (copy of the rows to LDS) %.0f\n", (double)h[2100] / h[2108], (double)h[2101] / h[2108], (double)h[2102] / h[2108],
-                                  (double)h[2126] / h[2108], ((double)h[2109] - (double)h[2100] - (double)h[2101] - (double)h[2102] - (double)h[2126]) / h[2108]);
-    if (h[2104]) fprintf(stderr, "   broad-phase cross-check (dbg 16): %llu rows built by both scans, %llu differ (%llu longer, %llu shorter than the plain scan's; longest row %llu against %llu; partners in all %llu against %llu)\n",
-                         h[2104], h[2105], h[2120], h[2121], h[2122], h[2123], h[2124], h[2125]);
-    if (h[2103]) fprintf(stderr, "   prologue of the resident kernel, cycle sums of the first thread over all workgroup-launches: tables + first barrier %.3e | state load, zeroing, "
-                         "first control %.3e | rows_to_lds %.3e  = (its parts, incl. the calls after broad-phase runs) ordinal -> count loads + barrier %.3e | scan + allotment %.3e | copy + barrier %.3e\n",
-                         (double)h[2103], (double)h[2106], (double)h[2113], (double)h[2114], (double)h[2115], (double)h[2116]);
-    if (h[2142]) fprintf(stderr, "   tiled kernel, voxel phase of the first thread of every tile, cycle sums: six-direction sums %.3e | contacts %.3e | voxel update %.3e | pose granules out %.3e\n",
-                         (double)h[2140], (double)h[2141], (double)h[2142], (double)h[2143]);
-    if (h[2131]) fprintf(stderr, "   drag, facet pass (first thread, cycle sums): barrier behind the vertices %.3e | facet loop %.3e | barrier %.3e | per-voxel sums %.3e | barrier %.3e\n",
-                         (double)h[2130], (double)h[2131], (double)h[2132], (double)h[2133], (double)h[2134]);
-    static const char* names[6] = {"ctl+barA", "aux", "bond", "barB", "voxel", "barC+pub"};
-    static const char* tnames[8] = {"halo-wait", "bond", "svc:poll", "barB", "latch/rebuild", "voxel", "barC+mv", "svc:reduce+horizon"};
-    const bool tiled = !tile_launches.empty();
-    if (tiled && h[121]) fprintf(stderr, "robot barrier: %.2f poll rounds per barrier, %.0f cycles per barrier\n", (double)h[120] / h[121], (double)h[122] / h[121]);
-    for (int w = 0; w < 15; ++w) {
-        double tot = 0; for (int k = 0; k < (tiled ? 8 : 6); ++k) tot += (double)h[w * 8 + k];
-        if (tot == 0) continue;
-        fprintf(stderr, "wave %2d:", w);
-        if (tiled) for (int k = 0; k < 8; ++k) fprintf(stderr, " %s %5.1f%%", tnames[k], 100.0 * h[w * 8 + k] / tot);
-        else for (int k = 0; k < 6; ++k) fprintf(stderr, " %s %5.1f%%", names[k], 100.0 * h[w * 8 + k] / tot);
-        fprintf(stderr, "  total %.3e cycles", tot);
-        if (!tiled && h[w * 8 + 6] + h[w * 8 + 7]) fprintf(stderr, "  (MESH: mesh vertices / facets inside aux; else: before the step loop / after it, cycles)  %.3e  %.3e", (double)h[w * 8 + 6], (double)h[w * 8 + 7]);
-        fprintf(stderr, "\n");
-    }
+    std::vector<unsigned long long> h(VXH_PROF_WORDS);
+    HIP_OK(hipMemcpy(h.data(), B.prof, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
+    vxh::report_phase_counters(h.data(), B.n_tiles, !tile_launches.empty());
 }
 #endif
 
@@ -657,8 +580,7 @@ void Engine::prepare()
             for (int k = 0; k < 2; ++k) g.order_bits[k] = D.alloc_zero<unsigned long long>((size_t)(g.count + 63) / 64 + 1);
             g.order_perm = (int*)D.alloc_zero<unsigned long long>((size_t)order_ws_words(g.count));
             // the ordering kernel once, here: its first launch loads its code, 0.4 ms that would otherwise fall into the first long call
-            hipLaunchKernelGGL(k_dispatch_order, dim3((g.count + VXH_ORDER_BLOCK - 1) / VXH_ORDER_BLOCK), dim3(VXH_ORDER_BLOCK), 0, D.stream,
-                               order_ws_cost(g.order_perm, g.count), g.count, 0, g.order_perm);
+            launch_dispatch_order(order_ws_cost(g.order_perm, g.count), g.count, 0, g.order_perm, D.stream);
         }
         D.give_stream(g, gi);
     }
@@ -666,7 +588,7 @@ void Engine::prepare()
     D.reb_robot = D.upload(P.reb_robot);
     D.reb_i0 = D.upload(P.reb_i0);
 #ifdef VXH_PHASE_TIMING
-    B.prof = D.alloc_zero<unsigned long long>(16 * 8 + 256 * 8);
+    B.prof = D.alloc_zero<unsigned long long>(VXH_PROF_WORDS);
 #endif
     B.small_angle_w = std::cos(VXH_SMALL_ANGLE_RAD * 0.5);                    // Vec3D.h:55-59
     B.smallish_angle_w = std::cos(VXH_HYST * VXH_SMALL_ANGLE_RAD * 0.5);
@@ -793,8 +715,7 @@ void Engine::advance_launch(long long max_rounds)
                 const unsigned long long* order_in = dyn ? g.order_bits[g.order_cur] : nullptr;
                 if (measure) {
                     const bool by_cost = g.cost_valid && opt_.dispatch_order != 0;
-                    hipLaunchKernelGGL(k_dispatch_order, dim3((g.count + VXH_ORDER_BLOCK - 1) / VXH_ORDER_BLOCK), dim3(VXH_ORDER_BLOCK), 0, st,
-                                       order_ws_cost(g.order_perm, g.count), g.count, by_cost ? (int)len : 0, g.order_perm);
+                    launch_dispatch_order(order_ws_cost(g.order_perm, g.count), g.count, by_cost ? (int)len : 0, g.order_perm, st);
                     order_in = (const unsigned long long*)g.order_perm;
                     g.cost_valid = true; g.last_ordered = by_cost; g.last_len = len;
                 }
@@ -827,16 +748,7 @@ void Engine::advance_launch(long long max_rounds)
     }
     if (streaming) {
         if (tiled) HIP_OK(hipStreamWaitEvent(D.stream, D.tile_t1, 0));
-        const int nb_b = (3 * B.nv + 255) / 256, nb_v = (B.nv + 255) / 256;
-        auto round = [&](long long c) {
-            hipLaunchKernelGGL(k_step_begin, dim3(B.n_robots), dim3(256), 0, D.stream, B, c, 1);
-            if (D.any_fluid) {
-                hipLaunchKernelGGL(k_mesh_vertices, dim3((B.n_mv + 255) / 256), dim3(256), 0, D.stream, B);
-                hipLaunchKernelGGL(k_facets, dim3((B.n_facet + 255) / 256), dim3(256), 0, D.stream, B);
-            }
-            hipLaunchKernelGGL(k_bonds, dim3(nb_b + D.reb_blocks), dim3(256), 0, D.stream, B, nb_b, D.reb_robot, D.reb_i0);
-            hipLaunchKernelGGL(k_voxels, dim3(nb_v), dim3(256), 0, D.stream, B);
-        };
+        auto round = [&](long long c) { launch_stream_round(B, D.any_fluid, D.reb_blocks, D.reb_robot, D.reb_i0, D.stream, c); };
         long long launched = 0;
         if (opt_.graph_steps > 1 && cap == cap_all && todo >= opt_.graph_steps) {
             if (!D.graph_exec || D.graph_rounds != opt_.graph_steps || D.graph_mask != B.streamed) {
@@ -851,7 +763,7 @@ void Engine::advance_launch(long long max_rounds)
             while (todo - launched >= opt_.graph_steps) { HIP_OK(hipGraphLaunch(D.graph_exec, D.stream)); launched += opt_.graph_steps; }
         }
         for (; launched < todo; ++launched) round(cap);
-        hipLaunchKernelGGL(k_step_begin, dim3(B.n_robots), dim3(256), 0, D.stream, B, cap, 0);   // finish the last step
+        launch_stream_finish(B, D.stream, cap);
         launches += (D.any_fluid ? 5 : 3) * todo + 1;
     }
     if (fused && !single) for (auto& g : D.groups) HIP_OK(hipStreamWaitEvent(D.stream, g.t1, 0));
@@ -1066,7 +978,7 @@ void Engine::download_reduced()
     if (!control_downloaded_) download_control();
     if (nr > 0) {
         if (!D.results) D.results = D.alloc_zero<DResult>(nr);
-        hipLaunchKernelGGL(k_results, dim3(nr), dim3(256), 0, D.stream, D.B, D.results);
+        launch_results(D.B, nr, D.results, D.stream);
         HIP_OK(hipGetLastError());
         std::vector<DResult> h(nr);
         HIP_OK(hipMemcpyAsync(h.data(), D.results, sizeof(DResult) * nr, hipMemcpyDeviceToHost, D.stream));

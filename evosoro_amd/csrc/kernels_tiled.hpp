@@ -1,5 +1,5 @@
 // Tiled path of the batched Voxelyze stepper: k_tile_steps<TABG, MESH>, SEVERAL workgroups per robot, all of them resident for a
-// whole launch of many time steps (included at the end of kernels.hpp).  By default it steps the robots the one-workgroup-per-
+// whole launch of many time steps (built on kernels_group.hpp).  By default it steps the robots the one-workgroup-per-
 // robot kernel (kernels_fused.hpp) cannot take: lattices of more than 1024 voxels (BASELINE configs[4], one 20x20x20 robot).
 // With the option tile_small also small populations of large robots (measured to pay only there: engine.hip).  Loop being tiled:
 // CVX_Sim::Integrate, VX_Sim.cpp:1763-1933.
@@ -49,6 +49,10 @@
 // same inputs.  Residency: all tiles of a robot must be on the chip at the same time; the host sizes every launch to what the
 // CUs admit and issues the tiled launches of an engine on ONE stream.  Spins are bounded (VXH_ROBOT_SYNC_TIMEOUT).
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include "device_types.hpp"
+#include "kernels_group.hpp"
 
 namespace vxh {
 
@@ -172,7 +176,7 @@ __device__ __forceinline__ d3 tile_contacts(const DBatch& B, const DRobot& R, co
 }
 
 // CalcL1Bonds (VX_Sim.cpp:2357-2413) for the surface voxels a tile owns (worker thread t: surface ordinal `i` of its voxel, -1 =
-// none; every thread of the workgroup calls).  Like rebuild_rows (kernels.hpp) every row tests all surface voxels of the robot,
+// none; every thread of the workgroup calls).  Like rebuild_rows (kernels_physics.hpp) every row tests all surface voxels of the robot,
 // staged through LDS in chunks of CH from the exchange buffer, and keeps the accepted ones in ascending order.  Differences:
 //  * a chunk whose bounding box lies farther than the distance filter from the bounding box of the tile's own surface voxels is
 //    skipped by the whole workgroup (every pair in it would fail the filter: exact);
@@ -314,13 +318,13 @@ __device__ __forceinline__ int tile_rebuild(const DBatch& B, const DRobot& R, DR
 #ifdef VXH_PHASE_TIMING
 #define VXH_TT_DECL unsigned long long tt_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long tt_last = __builtin_readcyclecounter();
 #define VXH_TT_MARK(k) { const unsigned long long tt_now = __builtin_readcyclecounter(); tt_acc[k] += tt_now - tt_last; tt_last = tt_now; }
-#define VXH_TT_FLUSH if (B.prof && (threadIdx.x & 63) == 0) { for (int k = 0; k < 8; ++k) atomicAdd(&B.prof[(threadIdx.x >> 6) * 8 + k], tt_acc[k]); }
+#define VXH_TT_FLUSH if (B.prof && (threadIdx.x & 63) == 0) { for (int k = 0; k < 8; ++k) atomicAdd(&B.prof[VXH_PROF_WAVE + (threadIdx.x >> 6) * VXH_PROF_WAVE_WORDS + k], tt_acc[k]); }
 // ... and, at step VXH_TS_STEP of a launch, the real-time counter (100 MHz, common to all CUs) at the boundaries of the step, per tile
 #define VXH_TS_STEP 100
 // ... and cycle sums of the parts of the voxel phase, first thread of every tile (slots 2140 ..)
 #define VXH_TV_BEGIN unsigned long long t_tv = __builtin_readcyclecounter();
-#define VXH_TV(slot) { const unsigned long long t_now = __builtin_readcyclecounter(); if (B.prof && tid == 0) atomicAdd(&B.prof[2140 + (slot)], t_now - t_tv); t_tv = t_now; }
-#define VXH_TS(k, who) if (B.prof && it == VXH_TS_STEP && (who) && ti < 256) B.prof[128 + ti * 8 + (k)] = __builtin_amdgcn_s_memrealtime();
+#define VXH_TV(slot) { const unsigned long long t_now = __builtin_readcyclecounter(); if (B.prof && tid == 0) atomicAdd(&B.prof[VXH_PROF_TILE_VOXEL + (slot)], t_now - t_tv); t_tv = t_now; }
+#define VXH_TS(k, who) if (B.prof && it == VXH_TS_STEP && (who) && ti < VXH_PROF_TILE_COUNT) B.prof[VXH_PROF_TILE + ti * VXH_PROF_TILE_WORDS + (k)] = __builtin_amdgcn_s_memrealtime();
 #else
 #define VXH_TT_DECL
 #define VXH_TT_MARK(k)
@@ -537,7 +541,7 @@ __global__ __launch_bounds__(VXH_TILE_THREADS) void k_tile_steps(DBatch B, const
 
     // The serving wavefront's part of a step: wait until every tile of the robot has published its max |v|^2 for this step (= has
     // finished the previous one), reduce, note a divergence, else take the collision-horizon decision of the step -- UpdateCollisions,
-    // VX_Sim.cpp:1729-1755; the arithmetic of step_control_horizon (kernels.hpp), operation for operation.  What the decision reads of the
+    // VX_Sim.cpp:1729-1755; the arithmetic of step_control_horizon (kernels_physics.hpp), operation for operation.  What the decision reads of the
     // control block is fetched BEFORE the wait (nobody else writes those fields between two workgroup barriers) and what it leaves is stored
     // without being read back: behind the last poll stand a wave reduction, a square root, a division and stores -- the workgroup waits at
     // barrier (C) for exactly this lane (round 6; before: a dozen dependent LDS round trips, ~1 us).  `spec`: the step's snapshot of the
@@ -590,7 +594,7 @@ __global__ __launch_bounds__(VXH_TILE_THREADS) void k_tile_steps(DBatch B, const
             if (++spins > VXH_TILE_SPIN_LIMIT) { s_abort = 1; aborted = true; break; }
         }
 #ifdef VXH_PHASE_TIMING
-        if (B.prof && hz_thread) { atomicAdd(&B.prof[120], (unsigned long long)polls); atomicAdd(&B.prof[121], 1ull); atomicAdd(&B.prof[122], __builtin_readcyclecounter() - tp0); }
+        if (B.prof && hz_thread) { atomicAdd(&B.prof[VXH_PROF_BARRIER_POLLS], (unsigned long long)polls); atomicAdd(&B.prof[VXH_PROF_BARRIERS], 1ull); atomicAdd(&B.prof[VXH_PROF_BARRIER_CYCLES], __builtin_readcyclecounter() - tp0); }
 #endif
         double mvmax = 0.0;                   // max |v|^2 over the tiles; a negative word marks a tile in which a bond diverged
         bool neg = false;
@@ -630,7 +634,7 @@ __global__ __launch_bounds__(VXH_TILE_THREADS) void k_tile_steps(DBatch B, const
         VXH_TT_MARK(6)
         VXH_TS(0, tid == 0)
 #ifdef VXH_PHASE_TIMING
-        if (B.prof && it == VXH_TS_STEP + 1 && tid == 0 && ti < 256) B.prof[128 + ti * 8 + 6] = __builtin_amdgcn_s_memrealtime();   // (the next step's top, in the place of "control done")
+        if (B.prof && it == VXH_TS_STEP + 1 && tid == 0 && ti < VXH_PROF_TILE_COUNT) B.prof[VXH_PROF_TILE + ti * VXH_PROF_TILE_WORDS + 6] = __builtin_amdgcn_s_memrealtime();   // (the next step's top, in the place of "control done")
 #endif
         const unsigned ringn = ring == 2 ? 0 : ring + 1, ringp = ring == 0 ? 2 : ring - 1;
         const unsigned long long* const xq = B.xch + (size_t)ring * xbuf;      // poses at the start of this step
@@ -857,7 +861,7 @@ __global__ __launch_bounds__(VXH_TILE_THREADS) void k_tile_steps(DBatch B, const
                 return out;
             };
             if (valid) {
-                // ---- translation half: voxel_update_lin (kernels.hpp; CVXS_Voxel::EulerStep / CalcTotalForce, VXS_Voxel.cpp:169-427)
+                // ---- translation half: voxel_update_lin (kernels_physics.hpp; CVXS_Voxel::EulerStep / CalcTotalForce, VXS_Voxel.cpp:169-427)
                 d3 F = six_sums(0, tid);
                 VXH_TV(0)
                 d3 pos = mk3(ps[tid], ps[np + tid], ps[2 * np + tid]);

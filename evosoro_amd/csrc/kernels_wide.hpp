@@ -25,6 +25,10 @@
 //   cmask, rc_a1, rc_code   contact rows of colliding robots (rows_to_lds)
 //   ps'  [8][BLOCK]   (two_tiles) second pose tile, at the end: a step's new poses go into the tile nobody reads
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include "device_types.hpp"
+#include "kernels_group.hpp"
 
 namespace vxh {
 
@@ -327,7 +331,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void k_robot_wide(DBatch B, con
         __syncthreads();                       // (X) the voxel phase is complete: max |v|^2 in, the next step's control block written
         if (!two_tiles) store_poses();         // (every read of the old poses is done)
         VXH_T_MARK(5)
-        // the collision-horizon update of the NEXT step (step_control_horizon, kernels.hpp), by every thread for itself
+        // the collision-horizon update of the NEXT step (step_control_horizon, kernels_physics.hpp), by every thread for itself
         {
             const int nf = __builtin_amdgcn_readfirstlane(Knext.flags);
             bool reb = false;

@@ -1,6 +1,6 @@
-// Host-side launch entry points of the stepping kernels.  Each kernel family is its own translation unit (launch_fused_*.hip,
-// launch_wide.hip, launch_tiled.hip) so that the Makefile compiles them side by side and a change to one family
-// recompiles that family only; engine.hip (batch assembly, the call loop, the streaming kernels) sees these declarations.
+// Host-side launch entry points of every kernel.  Each kernel family is its own translation unit (launch_fused_*.hip,
+// launch_wide.hip, launch_tiled.hip, launch_stream.hip) so that the Makefile compiles them side by side and a change to one family
+// recompiles that family only; engine.hip (device memory, the call loop, graph capture) compiles no kernel and sees these declarations.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <mutex>
@@ -43,5 +43,14 @@ void launch_wide_group(const DBatch& B, bool mesh, bool tabg, const int* list, i
 void launch_tile_group(const DBatch& B, bool tabg, int mesh_kind, bool small, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters, unsigned gen);
 // threads of a tile's workgroup (the host sizes launches and LDS with the kernel's own constants)
 int tile_threads();
+// the streaming kernels (kernels_stream.hpp).  One time step of the streamed robots: k_step_begin, k_mesh_vertices and k_facets when any robot is
+// in a fluid, k_bonds (its blocks + reb_blocks broad-phase blocks: reb_robot / reb_i0), k_voxels ...
+void launch_stream_round(const DBatch& B, bool any_fluid, int reb_blocks, const int* reb_robot, const int* reb_i0, hipStream_t s, long long cap);
+// ... and the k_step_begin that finishes the last step of a call
+void launch_stream_finish(const DBatch& B, hipStream_t s, long long cap);
+// k_results: one DResult per robot
+void launch_results(const DBatch& B, int n_robots, DResult* out, hipStream_t s);
+// k_dispatch_order (kernels_order.hpp): perm = the `count` list entries by descending expected cost of a launch of `len` steps (0: the list order)
+void launch_dispatch_order(const DispatchCost* cost, int count, int len, int* perm, hipStream_t s);
 
 }  // namespace vxh

@@ -1,5 +1,5 @@
 // k_robot_steps, the _voxcad (no surface mesh) variants: one translation unit (launch.hpp)
-#include "kernels.hpp"
+#include "kernels_fused.hpp"
 #include "launch.hpp"
 
 namespace vxh {

@@ -1,5 +1,5 @@
 // k_robot_steps, the land_water (MESH) variants: one translation unit (launch.hpp)
-#include "kernels.hpp"
+#include "kernels_fused.hpp"
 #include "launch.hpp"
 
 namespace vxh {

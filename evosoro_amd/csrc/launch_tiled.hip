@@ -2,7 +2,7 @@
 #include <cstdlib>
 #include <mutex>
 #include <string>
-#include "kernels.hpp"
+#include "kernels_tiled.hpp"
 #include "launch.hpp"
 
 namespace vxh {

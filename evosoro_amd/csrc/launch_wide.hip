@@ -1,5 +1,5 @@
 // k_robot_wide: one translation unit (launch.hpp)
-#include "kernels.hpp"
+#include "kernels_wide.hpp"
 #include "launch.hpp"
 
 namespace vxh {

@@ -84,7 +84,7 @@ static qt q_from_angle_to_pos_x(v3 from)                                        
     double l = sqrt(n.x * n.x + n.y * n.y + n.z * n.z);                            /* NormalizeFast :117 */
     if (l > 0) { double li = 1.0 / l; n.x *= li; n.y *= li; n.z *= li; }
 #ifdef VXO_HALF_ANGLE
-    /* NOT the reference's evaluation: the same rotation written with the half-angle identities the HIP engine uses (kernels.hpp
+    /* NOT the reference's evaluation: the same rotation written with the half-angle identities the HIP engine uses (kernels_math.hpp
      * from_angle_to_pos_x; DESIGN.md "Numerics").  Built only into libvxoracle_ha.so, with which tests/test_gpu_ledger.py measures
      * how far THIS ONE rewrite moves the reference algorithm's own answer over a whole run. */
     if (n.x < -0.999999999999995) return Q(0, 0, 1, 0);

@@ -1,8 +1,8 @@
 #!/bin/bash
 # registers / scratch / occupancy of every kernel of the engine, as the compiler reports them (no GPU needed)
-# usage: scripts/kernel_resources.sh [-f family] [extra hipcc flags]     family: engine | launch_fused_land | launch_fused_mesh | launch_wide | launch_tiled (default: all)
+# usage: scripts/kernel_resources.sh [-f family] [extra hipcc flags]     family: launch_fused_land | launch_fused_mesh | launch_wide | launch_tiled | launch_stream (default: all)
 cd "$(dirname "$0")/../evosoro_amd/csrc"
-FAMS="engine launch_fused_land launch_fused_mesh launch_wide launch_tiled"
+FAMS="launch_fused_land launch_fused_mesh launch_wide launch_tiled launch_stream"
 if [ "$1" = "-f" ]; then FAMS="$2"; shift 2; fi
 for f in $FAMS; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -mllvm -disable-machine-licm "$@" --cuda-device-only -Rpass-analysis=kernel-resource-usage -c $f.hip -o /tmp/vxh_${f}_res.o 2>&1 &

@@ -10,11 +10,11 @@ the reference's own hexapus.vxa) and whose source had not been found.  It was fo
 the oracle put on the ENGINE's state before every step shows what one step of the two differs by -- 1e-12 voxel where a one-ulp
 change of the inputs moves the oracle by 2e-15): the back-rotation of a bond's forces through a rotation MATRIX that assumed a unit
 quaternion, where the reference's RotateVec3DInv carries |q|^2 -- and FromAngleToPosX's small-angle branch returns a quaternion of
-norm^2 1 + (y^2 + z^2)^2 / 4 (kernels.hpp RotInv).  With the diagonal corrected one step differs by 2e-15 voxel, the hexapus run ends
+norm^2 1 + (y^2 + z^2)^2 / 4 (kernels_math.hpp RotInv).  With the diagonal corrected one step differs by 2e-15 voxel, the hexapus run ends
 4e-14 voxel from the reference, and the term is gone.  Ruled out on the way, each as an instrument build of the oracle or a what-if
 build of the engine (drift .. drift6): FMA contraction, the half-angle form of FromAngleToPosX, the angle-addition form of the
 actuation sine, the damping constants folded with 1 / dt, a bond in different angle modes on the two sides; one other contributor
-was real and is pinned: 1 - w * w in ToRotationVector contracted into one FMA (kernels.hpp one_minus_square)."""
+was real and is pinned: 1 - w * w in ToRotationVector contracted into one FMA (kernels_math.hpp one_minus_square)."""
 import json
 import os
 

@@ -1142,7 +1142,7 @@ def test_one_step_from_the_same_state(eng_mod, golden_dir, manifest, kernel_path
     state before every step: oracle instrument vxo_set_state).  Differences of earlier steps cannot hide or feed anything here, so the
     bar can sit at the rounding level: 5e-14 voxel and 2e-11 of the largest velocity / angular velocity, step after step (measured
     2e-15 voxel, 3e-13, 1e-12; one-ulp noise on the oracle's own inputs gives 3e-15, 4e-13, 1.4e-12).  Round 3's systematic creep
-    was a formula difference of 1.2e-12 voxel per step in exactly this number (kernels.hpp RotInv) that 7806-step trajectories within
+    was a formula difference of 1.2e-12 voxel per step in exactly this number (kernels_math.hpp RotInv) that 7806-step trajectories within
     1e-10 voxel had not shown.
     Round 5: EVERY case of the parity ledger (tests/golden/manifest.json, 31 robots: all BASELINE configs at full size, both simulators,
     the 1000-voxel lattice of the 1024-thread variant, the shipped .vxa files), on each of the three kernel paths -- so that the

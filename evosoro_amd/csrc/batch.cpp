@@ -123,6 +123,27 @@ void lay_out_voxels(const std::vector<RobotModel>& robots, int variant, HostBatc
             H.total_trace += H.trace_cap[r];
         }
     }
+    // <NormDistByVol>: a volume per point of that trace, and the after-life / frozen traces (DBatch::trace_vol, xtrace), sized the same way
+    // from the spans in which UpdateStats can record them (VX_Sim.cpp:1549-1565): AfterlifeTime, MidLifeFreezeTime
+    H.vol_begin.assign(nr, 0);
+    H.total_vol = 0; H.total_xtrace = 0;
+    for (int k = 0; k < 2; ++k) { H.xt_begin[k].assign(nr, 0); H.xt_cap[k].assign(nr, 0); }
+    for (int r = 0; r < nr; ++r) {
+        const RobotModel& M = robots[r];
+        H.vol_begin[r] = H.total_vol;
+        for (int k = 0; k < 2; ++k) H.xt_begin[k][r] = H.total_xtrace;
+        if (!(variant == 0 && M.vxa.norm_dist_by_vol && H.trace_cap[r] > 0)) continue;
+        H.total_vol += H.trace_cap[r];
+        const double span[2] = { std::max(0.0, M.vxa.afterlife_time), std::max(0.0, M.vxa.midlife_freeze_time) };
+        for (int k = 0; k < 2; ++k) {
+            H.xt_begin[k][r] = H.total_xtrace;
+            if (!(span[k] > 0)) continue;
+            const double n = span[k] / M.vxa.time_between_traces + 8;
+            if (!(n < 4e6)) throw std::invalid_argument("TimeBetweenTraces asks for more than 4 million trace points");
+            H.xt_cap[k][r] = (int)n;
+            H.total_xtrace += H.xt_cap[k][r];
+        }
+    }
 
     H.wave_robot.assign(nv / 64, -1); H.nbr.assign((size_t)6 * nv, -1);
     H.surf.assign(std::max(ns, 1), 0); H.surf_code.assign(std::max(ns, 1), 0); H.surf_ord.assign(nv, -1);
@@ -410,7 +431,8 @@ void robot_scalars(const RobotModel& M, int r, int variant, HostBatch& H)
               ((X.col_system == 2 || X.col_system == 3) ? RF_HORIZON_COL : 0) |
               (M.development ? RF_DEV : 0) | ((X.has_initial_voxel_size || X.has_final_voxel_size) ? RF_DEV_SIZE : 0) |
               (X.has_final_voxel_size ? RF_DEV_FSIZE : 0) | (X.has_final_phase_offset ? RF_DEV_FPHASE : 0) |
-              (X.has_final_temp_amp_damp ? RF_DEV_FTAD : 0);
+              (X.has_final_temp_amp_damp ? RF_DEV_FTAD : 0) |
+              ((variant == 0 && X.norm_dist_by_vol && H.trace_cap[r] > 0) ? RF_NORM_VOL : 0);
     R.stop_type = X.stop_type;
     R.dt = M.dt; R.lat = X.lattice_dim; R.bond_z_half = 0.5 * X.bond_damping_z; R.slow_z = X.slow_damping_z; R.col_z = X.col_damping_z;
     R.grav_acc = X.grav_acc; R.init_cm_time = X.init_cm_time; R.stop_value = X.stop_value;
@@ -421,6 +443,8 @@ void robot_scalars(const RobotModel& M, int r, int variant, HostBatch& H)
     R.drag_coef = X.aggregate_drag_coef;
     R.midlife_freeze_time = X.midlife_freeze_time;
     R.trace_dt = H.trace_cap[r] > 0 ? X.time_between_traces : 0.0; R.trace_begin = H.trace_begin[r]; R.trace_cap = H.trace_cap[r];
+    R.vol_begin = H.vol_begin[r];
+    for (int k = 0; k < 2; ++k) { R.xt_begin[k] = H.xt_begin[k][r]; R.xt_cap[k] = H.xt_cap[k][r]; }
     R.temp_amplitude = (float)X.temp_amplitude; R.temp_period = (float)X.temp_period;
     DRobotState& S = H.rstate[r];
     std::memset(&S, 0, sizeof(S));

@@ -33,6 +33,10 @@ struct HostBatch {
     std::vector<int> vox_begin, surf_begin;    // per robot, global slot of voxel 0 / of its first surface voxel
     std::vector<int> trace_begin, trace_cap;   // per robot, entries of DBatch::trace
     int total_trace = 0;
+    // robots with <NormDistByVol>: volumes of those points (DBatch::trace_vol), after-life [0] and frozen [1] traces (DBatch::xtrace); every
+    // other robot has empty ranges
+    std::vector<int> vol_begin, xt_begin[2], xt_cap[2];
+    int total_vol = 0, total_xtrace = 0;
     long long max_planned = 0;
     int max_nvox = 0;                          // largest robot of the batch
     std::vector<DVoxClass> vtab;

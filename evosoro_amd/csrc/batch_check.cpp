@@ -288,8 +288,8 @@ void same_values(const char* what, const std::vector<T>& a, const std::vector<T>
 // (bytewise: only for structs without padding)
 static_assert(sizeof(DVoxClass) == 12 * sizeof(double) + 2 * sizeof(int), "DVoxClass has padding");
 static_assert(sizeof(DBondClass) == 20 * sizeof(double) + 2 * sizeof(int), "DBondClass has padding");
-static_assert(sizeof(DRobot) == 24 * sizeof(int) + 2 * sizeof(long long) + 17 * sizeof(double) + 2 * sizeof(float), "DRobot has padding");
-static_assert(sizeof(DRobotState) == 11 * sizeof(double) + sizeof(unsigned long long) + 12 * sizeof(int), "DRobotState has padding");
+static_assert(sizeof(DRobot) == 30 * sizeof(int) + 2 * sizeof(long long) + 17 * sizeof(double) + 2 * sizeof(float), "DRobot has padding");
+static_assert(sizeof(DRobotState) == 13 * sizeof(double) + sizeof(unsigned long long) + 14 * sizeof(int), "DRobotState has padding");
 template <class T>
 void same_bytes(const char* what, const std::vector<T>& a, const std::vector<T>& b)
 {
@@ -302,10 +302,10 @@ void same_batch(const HostBatch& a, const HostBatch& b)
 #define SCALAR(f) CHECK(a.f == b.f, #f " differs")
 #define VALUES(f) same_values(#f, a.f, b.f)
 #define BYTES(f) same_bytes(#f, a.f, b.f)
-    SCALAR(nv); SCALAR(ns); SCALAR(total_trace); SCALAR(max_planned); SCALAR(max_nvox); SCALAR(any_dev); SCALAR(any_mesh); SCALAR(any_fluid);
+    SCALAR(nv); SCALAR(ns); SCALAR(total_trace); SCALAR(total_vol); SCALAR(total_xtrace); SCALAR(max_planned); SCALAR(max_nvox); SCALAR(any_dev); SCALAR(any_mesh); SCALAR(any_fluid);
     SCALAR(total_mv); SCALAR(total_facet); SCALAR(col_total);
     BYTES(robot); BYTES(rstate); BYTES(vtab); BYTES(btab);
-    VALUES(vox_begin); VALUES(surf_begin); VALUES(trace_begin); VALUES(trace_cap); VALUES(wave_robot); VALUES(nbr); VALUES(surf); VALUES(surf_code);
+    VALUES(vox_begin); VALUES(surf_begin); VALUES(trace_begin); VALUES(trace_cap); VALUES(vol_begin); VALUES(xt_begin[0]); VALUES(xt_begin[1]); VALUES(xt_cap[0]); VALUES(xt_cap[1]); VALUES(wave_robot); VALUES(nbr); VALUES(surf); VALUES(surf_code);
     VALUES(surf_ord); VALUES(excl); VALUES(vclass); VALUES(bclass); VALUES(sched_off); VALUES(bsched); VALUES(wl_off); VALUES(wlist); VALUES(wgather);
     VALUES(amp_damp); VALUES(dev); VALUES(act_sb); VALUES(act_cb); VALUES(px); VALUES(py); VALUES(pz); VALUES(sc); VALUES(qw); VALUES(small);
     VALUES(mv_begin); VALUES(facet_begin); VALUES(vert_pack); VALUES(vert_vox); VALUES(vert_robot); VALUES(vert_v0); VALUES(facet_vox); VALUES(facet_vert);

@@ -269,7 +269,8 @@ int vxh_write_result_xml(const vxh_engine* ce, int robot, const char* path_or_nu
                 shape_end = vxh::shape_complexity_as_the_reference_prints_it(m, ex_end);
             }
         }
-        text = vxh::result_xml(m, res, e->impl->trace_of(robot), shape_start, shape_end);
+        const vxh::HostState& traces = e->impl->traces_of(robot);
+        text = vxh::result_xml(m, res, traces.cm_trace, shape_start, shape_end, traces.vol_trace);
     });
     // land_water: the final mesh's per-vertex angle excesses into <CurvaturesTmpFile>, tab-separated with the stream's six
     // significant digits, as CVX_MeshUtil::computeShapeComplexity leaves them for curvatureEntropy.py (LW/VX_MeshUtil.cpp:1016-1031;
@@ -356,6 +357,20 @@ int vxh_get_cm_trace(const vxh_engine* ce, int robot, double* out4n, int capacit
     vxh_engine* e = const_cast<vxh_engine*>(ce);
     if (bad_robot(e, robot) || capacity < 0 || (capacity > 0 && !out4n)) return VXH_ERR_ARG;
     return guarded(e, [&] { const int n = e->impl->cm_trace(robot, out4n, capacity); if (count_out) *count_out = n; });
+}
+
+int vxh_get_cm_trace_of(const vxh_engine* ce, int robot, int which, double* out4n, int capacity, int* count_out)
+{
+    vxh_engine* e = const_cast<vxh_engine*>(ce);
+    if (bad_robot(e, robot) || which < 0 || which > 2 || capacity < 0 || (capacity > 0 && !out4n)) return VXH_ERR_ARG;
+    return guarded(e, [&] { const int n = e->impl->cm_trace_of(robot, which, out4n, capacity); if (count_out) *count_out = n; });
+}
+
+int vxh_get_volume_trace(const vxh_engine* ce, int robot, int which, double* out2n, int capacity, int* count_out)
+{
+    vxh_engine* e = const_cast<vxh_engine*>(ce);
+    if (bad_robot(e, robot) || which < 0 || which > 2 || capacity < 0 || (capacity > 0 && !out2n)) return VXH_ERR_ARG;
+    return guarded(e, [&] { const int n = e->impl->volume_trace(robot, which, out2n, capacity); if (count_out) *count_out = n; });
 }
 
 int vxh_count_bond_modes(const vxh_engine* ce, long long* large_angle_out, long long* total_out)

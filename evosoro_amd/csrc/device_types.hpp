@@ -34,7 +34,11 @@ struct DBondClass {
 enum RobotFlags { RF_SELF_COL = 1, RF_GRAV = 2, RF_FLOOR = 4, RF_TEMP = 8, RF_STICKY = 16, RF_FLUID = 32, RF_LW = 64,
                   RF_HORIZON_COL = 128,
                   // _voxcad development (VXS_Voxel.cpp:236-328): any layer present / which ones
-                  RF_DEV = 256, RF_DEV_SIZE = 512 /* Initial- or FinalVoxelSize */, RF_DEV_FSIZE = 1024, RF_DEV_FPHASE = 2048, RF_DEV_FTAD = 4096 };
+                  RF_DEV = 256, RF_DEV_SIZE = 512 /* Initial- or FinalVoxelSize */, RF_DEV_FSIZE = 1024, RF_DEV_FPHASE = 2048, RF_DEV_FTAD = 4096,
+                  // <NormDistByVol> (VX_Sim.cpp:1568-1597): the traces carry the robot's volume, and the after-life and frozen traces are kept
+                  RF_NORM_VOL = 8192 };
+// the three traces of UpdateStats (VX_Sim.cpp:1537-1597) as bits of a step's trace mask, and as the `which` of the C ABI
+enum { VXH_TRACE_LIFE = 0, VXH_TRACE_AFTERLIFE = 1, VXH_TRACE_FROZEN = 2 };
 
 enum { VXH_ORDER_MAX_STEPS = 128,    // launches of at most this many steps are dispatched "robots due for a broad-phase run first", longer ones by measured cost (kernels_fused.hpp)
        VXH_ORDER_HORIZON = 32 };     // ... and what a longer launch calls "due" when it leaves the flags for the launch behind it
@@ -57,6 +61,9 @@ struct DRobot {               // constant per robot
     double midlife_freeze_time;
     double trace_dt;              // <TimeBetweenTraces>, 0 = no centre-of-mass trace
     int trace_begin, trace_cap;   // this robot's entries of DBatch::trace
+    // RF_NORM_VOL robots: the volumes of those points in DBatch::trace_vol (vol_begin; as many as trace_cap), and the after-life [0] and
+    // frozen [1] traces in DBatch::xtrace (all zero for every other robot)
+    int vol_begin, xt_begin[2], xt_cap[2], pad_xt;
     float temp_amplitude, temp_period;
     long long col_begin;          // first entry of this robot's block of contact rows in DBatch::col_partner / col_a1 / col_code
     int col_cap;
@@ -82,6 +89,10 @@ struct DRobotState {          // mutable per robot
     double last_trace_time;
     double act_time;              // resident / wide / tiled kernels: act_sin / act_cos are those of this simulated time (stashed at the end of a launch
                                   // for the first step of the next one; -1: nothing stashed)
+    // RF_NORM_VOL robots: last point and number of points of the after-life [0] and the frozen [1] trace (SS.CMTraceTimeAfterLife /
+    // SS.CMTraceTimeWhileFrozen, VX_Sim.cpp:1549-1565), each with the cadence of its own
+    double last_xtrace_time[2];
+    int nxtrace[2];
 };
 
 // Tiled path (kernels_tiled.hpp): a robot cut into `ntiles` tiles, one workgroup each.  A tile OWNS n_own voxels (it
@@ -297,6 +308,8 @@ struct DBatch {
     int* tile_xh;                     // [total tiles][VXH_TILE_XH] contact partners owned by other tiles that the tile mirrors (global slots)
     int* tile_xhn;                    // [total tiles] their number
     double* trace;                    // centre-of-mass traces: 4 doubles (time, x, y, z) per entry, robots one after the other (DRobot::trace_begin)
+    double* trace_vol;                // RF_NORM_VOL robots: getTotalVolume() at every point of `trace`, one double per entry (DRobot::vol_begin)
+    double* xtrace;                   // ... and their after-life and frozen traces: 5 doubles (time, x, y, z, volume) per entry (DRobot::xt_begin)
     unsigned long long* prof;         // developer builds (-DVXH_PHASE_TIMING): [VXH_PROF_WORDS] counters (ProfSlot above), else null
     // constants from Vec3D.h evaluated by the host libm (thresholds of the small-angle logic)
     double small_angle_w, smallish_angle_w, slthresh_acos2sqrt;

@@ -83,6 +83,8 @@ struct Engine::Device {
     std::vector<int> vox_begin;           // per robot, global slot of voxel 0
     std::vector<int> trace_begin, trace_cap;   // per robot, entries of DBatch::trace
     int total_trace = 0;
+    std::vector<int> vol_begin, xt_begin[2], xt_cap[2];   // robots with <NormDistByVol>: entries of DBatch::trace_vol / xtrace (HostBatch)
+    int total_vol = 0, total_xtrace = 0;
     std::vector<int> surf_begin;
     int total_surf = 0;
     long long max_planned = 0;
@@ -528,6 +530,8 @@ void Engine::prepare()
     B.fdrag = D.alloc_zero<double>(H.any_fluid ? (size_t)3 * std::max(H.total_facet, 1) : 1);
     D.any_fluid = H.any_fluid;
     B.trace = D.alloc_zero<double>((size_t)std::max(H.total_trace, 1) * 4);
+    B.trace_vol = D.alloc_zero<double>((size_t)std::max(H.total_vol, 1));
+    B.xtrace = D.alloc_zero<double>((size_t)std::max(H.total_xtrace, 1) * 5);
     B.col_rows = std::max(ns, 1);
     B.col_cnt = D.alloc_zero<int>(std::max(ns, 1));
     {   // saved LDS images of the contact rows (resident kernel): one slot per colliding robot of up to 1024 voxels
@@ -599,6 +603,8 @@ void Engine::prepare()
     D.h_robot = std::move(H.robot);
     D.vox_begin = std::move(H.vox_begin); D.surf_begin = std::move(H.surf_begin); D.total_surf = ns;
     D.trace_begin = std::move(H.trace_begin); D.trace_cap = std::move(H.trace_cap); D.total_trace = H.total_trace;
+    D.vol_begin = std::move(H.vol_begin); D.total_vol = H.total_vol; D.total_xtrace = H.total_xtrace;
+    for (int k = 0; k < 2; ++k) { D.xt_begin[k] = std::move(H.xt_begin[k]); D.xt_cap[k] = std::move(H.xt_cap[k]); }
     D.max_planned = H.max_planned; D.max_nvox = H.max_nvox;
     D.robot_tiled = std::move(P.robot_tiled); D.robot_tiles = std::move(P.robot_tiles);
     hs.mark("kernel choice, tiling, launch groups");
@@ -857,6 +863,9 @@ void Engine::download_control(bool already_copied)
         H.cur_time = S.cur_time; H.steps = S.steps; H.status = S.status; H.cm_init = S.cm_init; H.rebuilds = S.rebuilds;
         H.eol_post_y = S.eol_post_y;
         H.cm_trace.assign((size_t)4 * std::min(S.ntrace, D.trace_cap[r]), 0.0);      // (filled by download())
+        const bool norm_vol = variant_ == 0 && M.vxa.norm_dist_by_vol && D.trace_cap[r] > 0;      // (RF_NORM_VOL, batch.cpp)
+        H.vol_trace.assign(norm_vol ? H.cm_trace.size() / 4 : 0, 0.0);
+        for (int k = 0; k < 2; ++k) H.xtrace[k].assign((size_t)5 * std::min(S.nxtrace[k], D.xt_cap[k][r]), 0.0);
         for (int k = 0; k < 3; ++k) H.ini_cm[k] = S.ini_cm[k];
         if (S.col_overflow) H.status = VXH_ROBOT_COL_OVERFLOW;
         if (S.status == 5 || (r == 0 && inject_tile_timeout_ > 0 && !D.tile_launches.empty() && --inject_tile_timeout_ == 0)) {
@@ -924,6 +933,38 @@ int Engine::cm_trace(int robot, double* out4n, int capacity)
     const std::vector<double>& t = trace_of(robot);
     const int n = (int)(t.size() / 4);
     for (int k = 0; k < std::min(n, capacity) * 4; ++k) out4n[k] = t[k];
+    return n;
+}
+
+const HostState& Engine::traces_of(int robot)
+{
+    trace_of(robot);
+    return host_[robot];
+}
+
+int Engine::cm_trace_of(int robot, int which, double* out4n, int capacity)
+{
+    if (which == VXH_TRACE_LIFE) return cm_trace(robot, out4n, capacity);
+    if (which != VXH_TRACE_AFTERLIFE && which != VXH_TRACE_FROZEN) throw std::invalid_argument("which: 0 life, 1 after-life, 2 frozen");
+    const std::vector<double>& t = traces_of(robot).xtrace[which - 1];
+    const int n = (int)(t.size() / 5);
+    for (int i = 0; i < std::min(n, capacity); ++i)
+        for (int k = 0; k < 4; ++k) out4n[4 * i + k] = t[(size_t)5 * i + k];
+    return n;
+}
+
+int Engine::volume_trace(int robot, int which, double* out2n, int capacity)
+{
+    if (which < VXH_TRACE_LIFE || which > VXH_TRACE_FROZEN) throw std::invalid_argument("which: 0 life, 1 after-life, 2 frozen");
+    const HostState& H = traces_of(robot);
+    if (which == VXH_TRACE_LIFE) {
+        const int n = (int)H.vol_trace.size();
+        for (int i = 0; i < std::min(n, capacity); ++i) { out2n[2 * i] = H.cm_trace[(size_t)4 * i]; out2n[2 * i + 1] = H.vol_trace[i]; }
+        return n;
+    }
+    const std::vector<double>& t = H.xtrace[which - 1];
+    const int n = (int)(t.size() / 5);
+    for (int i = 0; i < std::min(n, capacity); ++i) { out2n[2 * i] = t[(size_t)5 * i]; out2n[2 * i + 1] = t[(size_t)5 * i + 4]; }
     return n;
 }
 
@@ -996,6 +1037,17 @@ void Engine::download_reduced()
         for (int r = 0; r < nr; ++r)
             for (size_t k = 0; k < host_[r].cm_trace.size(); ++k) host_[r].cm_trace[k] = tr[(size_t)D.trace_begin[r] * 4 + k];
     }
+    if (D.total_vol > 0) {                 // robots with <NormDistByVol>: the volumes of those points, the after-life and frozen traces
+        std::vector<double> tv((size_t)D.total_vol), tx((size_t)std::max(D.total_xtrace, 1) * 5);
+        HIP_OK(hipMemcpy(tv.data(), D.B.trace_vol, sizeof(double) * tv.size(), hipMemcpyDeviceToHost));
+        if (D.total_xtrace > 0) HIP_OK(hipMemcpy(tx.data(), D.B.xtrace, sizeof(double) * tx.size(), hipMemcpyDeviceToHost));
+        for (int r = 0; r < nr; ++r) {
+            HostState& H = host_[r];
+            for (size_t k = 0; k < H.vol_trace.size(); ++k) H.vol_trace[k] = tv[(size_t)D.vol_begin[r] + k];
+            for (int w = 0; w < 2; ++w)
+                for (size_t k = 0; k < H.xtrace[w].size(); ++k) H.xtrace[w][k] = tx[(size_t)D.xt_begin[w][r] * 5 + k];
+        }
+    }
     reduced_downloaded_ = true;
 }
 
@@ -1007,6 +1059,7 @@ void Engine::result(int robot, vxh_result* out)
     const bool need_state = variant_ == 1 || opt_.host_results;
     if (need_state && !state_downloaded_) download();
     if (!need_state && !reduced_downloaded_) download_reduced();
+    if (variant_ == 0 && robots_[robot].vxa.norm_dist_by_vol && !reduced_downloaded_) download_reduced();   // (the traces the Norm tags are summed from)
     HostState& H = host_[robot];
     if (need_state) { const bool keep = H.reduced; H.reduced = false; compute_result(robots_[robot], H, out); H.reduced = keep; }
     else compute_result(robots_[robot], H, out);

@@ -24,6 +24,9 @@ struct HostState {                      // final/current state of one robot, dow
     double red_cm[3] = {0, 0, 0}, d2max = 0, d2min = 0, ymax = 0, ymin = 0;
     int touching = 0, feet = 0;
     std::vector<double> cm_trace;                              // [4*k] (time, x, y, z): SS.CMTraceTime / SS.CMTrace
+    // robots with <NormDistByVol>: SS.VolTrace, a volume per point of cm_trace, and the after-life [0] / frozen [1] traces,
+    // [5*k] (time, x, y, z, volume): SS.CMTraceAfterLife + SS.VolTraceAfterLife, SS.CMTraceWhileFrozen + SS.VolTraceWhileFrozen
+    std::vector<double> vol_trace, xtrace[2];
 };
 
 // the tiles of a robot gave up waiting for each other (VXH_ROBOT_SYNC_TIMEOUT): Engine::advance makes a call that started from the
@@ -73,6 +76,10 @@ public:
     void state14(int robot, double* out, int capacity);
     void counters(vxh_counters* out) const { *out = counters_; }
     int cm_trace(int robot, double* out4n, int capacity);      // returns the number of points recorded
+    // which = 0 life, 1 after-life, 2 frozen (the last two exist for robots with <NormDistByVol>): (time, x, y, z) / (time, volume) per point
+    int cm_trace_of(int robot, int which, double* out4n, int capacity);
+    int volume_trace(int robot, int which, double* out2n, int capacity);
+    const HostState& traces_of(int robot);                     // cm_trace, vol_trace, xtrace of the robot (downloads them if needed)
     std::vector<double> angle_excess(int robot, bool at_end);  // land_water: discrete curvature of every mesh vertex, rest state / current state
     void shape(int robot, bool at_end, struct MeshShape& out); // the surface mesh and its descriptors, rest state / current state
     void bond_modes(long long* large_angle, long long* total);   // SmallAngle flags of every bond, downloaded
@@ -141,6 +148,9 @@ public:
     void set_option(const std::string& key, double value);
     int cm_trace(int robot, double* out4n, int capacity);
     const std::vector<double>& trace_of(int robot);
+    int cm_trace_of(int robot, int which, double* out4n, int capacity);
+    int volume_trace(int robot, int which, double* out2n, int capacity);
+    const HostState& traces_of(int robot);
     std::vector<double> angle_excess(int robot, bool at_end);
     void shape(int robot, bool at_end, struct MeshShape& out);
     void bond_modes(long long* large_angle, long long* total);
@@ -168,9 +178,13 @@ int hip_device_count();      // engine.hip: HIP devices this process can use (0 
 
 // results.cpp: the numbers of CVX_SimGA::WriteResultFile from a final state, and the XML text
 void compute_result(const RobotModel& model, const HostState& st, vxh_result* out);
-std::string result_xml(const RobotModel& model, const vxh_result& res, const std::vector<double>& cm_trace, double shape_start = -1.0, double shape_end = -1.0);
-double shape_complexity_as_the_reference_prints_it(const RobotModel& model, const std::vector<double>& angle_excess);
 const std::vector<double>& empty_trace();
+std::string result_xml(const RobotModel& model, const vxh_result& res, const std::vector<double>& cm_trace, double shape_start = -1.0, double shape_end = -1.0,
+                       const std::vector<double>& vol_trace = empty_trace());
+// results.cpp: one sum of WriteResultFile under <NormDistByVol> (VX_SimGA.cpp:57-112) over a trace of n points, y and volume of point i at
+// y[i * y_stride] and vol[i * vol_stride]; 0 for a trace of fewer than two points
+double norm_dist_by_vol(size_t n, const double* y, size_t y_stride, const double* vol, size_t vol_stride, double lattice_dim, double exponent);
+double shape_complexity_as_the_reference_prints_it(const RobotModel& model, const std::vector<double>& angle_excess);
 double convex_hull_volume(const std::vector<double>& xyz);   // results.cpp: what stands in for the reference's external qhull
 // results.cpp: per-vertex angle excess of the surface mesh (LW/VX_MeshUtil.cpp:956-1014); pos / quat / strain null = the rest state
 void mesh_angle_excess(const RobotModel& model, const double* pos, const double* quat, const double* strain, std::vector<double>& out);

@@ -209,6 +209,21 @@ const std::vector<double>& EngineSet::trace_of(int robot)
     flush_pending(); distribute();
     return engines_[where_[robot].first]->trace_of(where_[robot].second);
 }
+int EngineSet::cm_trace_of(int robot, int which, double* out4n, int capacity)
+{
+    flush_pending(); distribute();
+    return engines_[where_[robot].first]->cm_trace_of(where_[robot].second, which, out4n, capacity);
+}
+int EngineSet::volume_trace(int robot, int which, double* out2n, int capacity)
+{
+    flush_pending(); distribute();
+    return engines_[where_[robot].first]->volume_trace(where_[robot].second, which, out2n, capacity);
+}
+const HostState& EngineSet::traces_of(int robot)
+{
+    flush_pending(); distribute();
+    return engines_[where_[robot].first]->traces_of(where_[robot].second);
+}
 std::vector<double> EngineSet::angle_excess(int robot, bool at_end)
 {
     flush_pending(); distribute();

@@ -104,7 +104,7 @@ __global__ __launch_bounds__(BLOCK, (BLOCK + 255) / 256) void k_robot_steps(DBat
     __shared__ FusedCtl s_ctl[2];
     __shared__ int s_div, s_na[3], s_seg[2 * (BLOCK / 64)];
     __shared__ std::conditional_t<COST, FusedCostLds, FusedNoLds> s_cost;
-    static_assert(sizeof(DRobotState) + 2 * sizeof(FusedCtl) + 5 * sizeof(int) + 2 * 16 * sizeof(int) + sizeof(FusedCostLds) + 16 <= VXH_FUSED_STATIC_LDS, "static LDS bound");
+    static_assert(sizeof(DRobotState) + 2 * sizeof(FusedCtl) + 4 * sizeof(int) /* s_div, s_na */ + 2 * 16 * sizeof(int) + sizeof(FusedCostLds) + 16 <= VXH_FUSED_STATIC_LDS, "static LDS bound");
 
     const int tid = threadIdx.x;
     VXH_T_PRO_BEGIN
@@ -295,7 +295,7 @@ __global__ __launch_bounds__(BLOCK, (BLOCK + 255) / 256) void k_robot_steps(DBat
         const FusedCtl& K = s_ctl[it & 1];
         FusedCtl& Knext = s_ctl[(it + 1) & 1];
         const int kf = __builtin_amdgcn_readfirstlane(K.flags);
-        const bool k_go = kf & 1, k_latch = kf & 2, k_eol = kf & 4, k_rebuild = kf & 8, k_trace = kf & 16;
+        const bool k_go = kf & 1, k_latch = kf & 2, k_eol = kf & 4, k_rebuild = kf & 8, k_trace = kf & VXH_CTL_TRACE_BITS;
         if (!k_go && !k_trace) break;
         // opaque per-step copies: keeps the compiler from hoisting every address of the step out of the loop (dozens of
         // loop-invariant 64-bit pointers, which it then spills)
@@ -303,7 +303,7 @@ __global__ __launch_bounds__(BLOCK, (BLOCK + 255) / 256) void k_robot_steps(DBat
         asm volatile("" : "+v"(vv));
         bool scratch_used = false;            // latch / broad-phase borrow the accumulator tile
         if (k_latch || k_eol || k_trace) {
-            fused_latch_cm<BLOCK>(R, rs, ps, acc, valid, C, k_latch, k_eol, k_trace, B.trace + (size_t)(R.trace_begin + K.trace_index) * 4);
+            fused_latch_cm<BLOCK>(B, R, rs, ps, acc, valid, C, k_latch, k_eol, fused_trace_mask(kf), K.trace_index);
             scratch_used = true;
         }
         if (!k_go) break;                      // (the robot has stopped; the last step's trace point, if one was due, is in)

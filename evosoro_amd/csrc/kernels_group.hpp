@@ -82,9 +82,10 @@ __device__ __forceinline__ void st_plane(double* base, unsigned plane, unsigned 
 }
 
 // IniCM latch + EndOfLifetimePosteriorY from the pose tile (see latch_cm in kernels_physics.hpp for the reference lines)
+// `tmask`: the traces that get a point (StepCtl::trace), `trace_index`: the life trace's entry
 template <int BLOCK>
-__device__ __forceinline__ void fused_latch_cm(const DRobot& R, DRobotState& rs, const double* ps, double* sh, bool valid,
-                                               const DVoxClass& C, bool latch, bool eol, bool trace, double* trace_entry)
+__device__ __forceinline__ void fused_latch_cm(const DBatch& B, const DRobot& R, DRobotState& rs, const double* ps, double* sh, bool valid,
+                                               const DVoxClass& C, bool latch, bool eol, int tmask, int trace_index)
 {
     const int tid = opaque_tid<BLOCK>();
     if (valid) sh[tid] = (C.mat == 5) ? -C.mass : C.mass;      // sign marks the material excluded from PosteriorY
@@ -100,7 +101,20 @@ __device__ __forceinline__ void fused_latch_cm(const DRobot& R, DRobotState& rs,
         }
         if (latch) { const double inv = 1.0 / sm; rs.ini_cm[0] = inv * sx; rs.ini_cm[1] = inv * sy; rs.ini_cm[2] = inv * sz; rs.cm_init = 1; }
         if (eol) rs.eol_post_y = miny;
-        if (trace) { const double inv = 1.0 / sm; trace_entry[0] = rs.cur_time; trace_entry[1] = inv * sx; trace_entry[2] = inv * sy; trace_entry[3] = inv * sz; }   // SS.CMTrace (VX_Sim.cpp:1537-1547)
+        if (tmask & (1 << VXH_TRACE_LIFE)) {   // SS.CMTrace (VX_Sim.cpp:1537-1547)
+            double* const trace_entry = B.trace + (size_t)(R.trace_begin + trace_index) * 4;
+            const double inv = 1.0 / sm; trace_entry[0] = rs.cur_time; trace_entry[1] = inv * sx; trace_entry[2] = inv * sy; trace_entry[3] = inv * sz;
+        }
+        // <NormDistByVol> (a flag of the robot): getTotalVolume() (VX_Sim.cpp:2574-2581) of the same poses, summed in voxel order by the same
+        // thread -- in a loop of its own, so that every other robot runs the loop above as it always has.  The cube is x * x * x, each product
+        // rounded (contraction is off here): at most an ulp per voxel from the reference's pow(x, 3), eleven orders below the six digits the
+        // result file prints.
+        if ((R.flags & RF_NORM_VOL) && tmask) {
+            double vol = 0;
+            for (int k = 0; k < R.nvox; ++k) { const double q = ps[3 * BLOCK + k] / R.lat; vol = vol + (q * q) * q; }
+            const double inv = 1.0 / sm;
+            store_norm_vol_points(B, R, rs, tmask, trace_index, inv * sx, inv * sy, inv * sz, vol);
+        }
     }
     __syncthreads();
 }
@@ -833,16 +847,19 @@ __device__ __forceinline__ d3 fused_contact_forces(const DBatch& B, const DRobot
     return F;
 }
 
-// `flags`: go | latch << 1 | eol << 2 | rebuild << 3 | trace << 4 | damp_on << 5 -- the resident kernel reads the step's decisions with one
-// LDS access instead of a chain of them
+// `flags`: go | latch << 1 | eol << 2 | rebuild << 3 | life trace << 4 | damp_on << 5 | after-life trace << 6 | frozen trace << 7 -- the resident
+// kernel reads the step's decisions with one LDS access instead of a chain of them (fused_trace_mask: the three trace bits as StepCtl::trace has
+// them).  `trace` is that mask.
 struct FusedCtl { double time, act_sin, act_cos, prenatal_c; int go, latch, eol, rebuild, damp_on, trace, trace_index, flags; };
+enum { VXH_CTL_TRACE_BITS = 16 | 64 | 128 };
+__device__ __forceinline__ int fused_trace_mask(int flags) { return ((flags >> 4) & 1) | ((flags >> 5) & 6); }
 
 __device__ __forceinline__ void fused_control_begin(const DRobot& R, DRobotState& rs, long long step_cap, int begin_new_step, FusedCtl& K)
 {
     const StepCtl c = step_control_begin(R, rs, step_cap, begin_new_step);
     K.go = c.go; K.latch = c.latch; K.eol = c.eol; K.rebuild = 0; K.trace = c.trace; K.trace_index = c.trace_index;
     K.time = rs.cur_time; K.damp_on = rs.dt_prev != 0;
-    K.flags = (c.go ? 1 : 0) | (c.latch ? 2 : 0) | (c.eol ? 4 : 0) | (c.trace ? 16 : 0) | (K.damp_on ? 32 : 0);
+    K.flags = (c.go ? 1 : 0) | (c.latch ? 2 : 0) | (c.eol ? 4 : 0) | ((c.trace & 1) << 4) | (K.damp_on ? 32 : 0) | ((c.trace & 6) << 5);
     K.prenatal_c = actuation_prenatal_c(R, rs.cur_time);
     K.act_sin = K.act_cos = 0;
     // sincos of the actuation phase: a chain of ~200 dependent FP64 instructions on one lane.  During a launch it hides behind the

@@ -464,7 +464,22 @@ __device__ __forceinline__ void actuation_sincos(const DRobot& R, double t, doub
 __device__ __forceinline__ double actuation_prenatal_c(const DRobot& R, double t) { return (t >= 0.5 * R.init_cm_time) ? 1.0 : 2 * t / R.init_cm_time; }
 
 // ------------------------------------------------------------------------------------- per-robot step control
+// `trace`: mask of the traces that get a point from this step (bit VXH_TRACE_LIFE / _AFTERLIFE / _FROZEN); `trace_index`: entry of the life trace
 struct StepCtl { int go, latch, eol, rebuild, trace, trace_index; };
+
+// One point of a RF_NORM_VOL robot's traces (executed by the one thread that holds the sums): the volume next to the life trace's entry,
+// a whole entry of the after-life / frozen trace.  `cm`: GetCM() of the step, `vol`: getTotalVolume().
+__device__ __forceinline__ void store_norm_vol_points(const DBatch& B, const DRobot& R, const DRobotState& rs, int mask, int life_index,
+                                                      double cx, double cy, double cz, double vol)
+{
+    if (mask & (1 << VXH_TRACE_LIFE)) B.trace_vol[R.vol_begin + life_index] = vol;
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+        if (mask & (2 << k)) {
+            double* e = B.xtrace + (size_t)(R.xt_begin[k] + rs.nxtrace[k] - 1) * 5;
+            e[0] = rs.cur_time; e[1] = cx; e[2] = cy; e[3] = cz; e[4] = vol;
+        }
+}
 
 // Executed by ONE thread per robot before every step (and once after the last): completes the previous step's
 // accounting, evaluates the stop condition and decides what this step needs.  Two parts: step_control_begin needs
@@ -476,12 +491,32 @@ __device__ __forceinline__ StepCtl step_control_begin(const DRobot& R, DRobotSta
     if (rs.active) {                         // finish the step the previous round computed
         if (rs.diverged) rs.status = 2;
         else {
+            const double t_before = rs.cur_time;
             rs.cur_time += R.dt; rs.steps += 1; rs.dt_prev = R.dt;
             // UpdateStats of that step (VX_Sim.cpp:1537-1547): a point of the centre-of-mass trace is due; the pass that latches
             // IniCM computes it from the poses the step left (also when the robot stops now: c.go stays 0, c.trace is set)
             if (R.trace_dt > 0 && rs.cur_time > R.init_cm_time && (rs.ntrace == 0 || rs.last_trace_time + R.trace_dt <= rs.cur_time)) {
-                if (rs.ntrace < R.trace_cap) { c.trace = 1; c.trace_index = rs.ntrace; }
+                if (rs.ntrace < R.trace_cap) { c.trace = 1 << VXH_TRACE_LIFE; c.trace_index = rs.ntrace; }
                 rs.ntrace += 1; rs.last_trace_time = rs.cur_time;
+            }
+            // <NormDistByVol>: the after-life and the frozen trace (:1549-1565, :1580-1596), each with the cadence of its own.  Their points go
+            // to entry nxtrace - 1 of the robot's range (latch_cm / fused_latch_cm read the index from the control block).  DevelopmentFrozen is
+            // what the top of that TimeStep set (:1090-1104) from the time BEFORE the step; UpdateStats uses it with the time after it.
+            if (R.flags & RF_NORM_VOL) {
+                bool due[2];
+                due[0] = R.afterlife > 0 && rs.cur_time > R.stop_value;
+                due[1] = false;
+                if (R.midlife_freeze_time > 0) {
+                    const double middle = 0.5 * (R.stop_value - R.init_cm_time);
+                    const double fs = middle - 0.5 * R.midlife_freeze_time, fe = middle + 0.5 * R.midlife_freeze_time;
+                    due[1] = t_before > fs + R.init_cm_time && t_before < fe;
+                }
+#pragma unroll
+                for (int k = 0; k < 2; ++k)
+                    if (due[k] && (rs.nxtrace[k] == 0 || rs.last_xtrace_time[k] + R.trace_dt <= rs.cur_time)) {
+                        if (rs.nxtrace[k] < R.xt_cap[k]) c.trace |= 2 << k;
+                        rs.nxtrace[k] += 1; rs.last_xtrace_time[k] = rs.cur_time;
+                    }
             }
         }
         rs.active = 0;
@@ -527,7 +562,7 @@ __device__ __forceinline__ StepCtl step_control(const DRobot& R, DRobotState& rs
 // and EndOfLifetimePosteriorY (getPosteriorY :2640-2656).  Whole workgroup; `sh` holds 5*CH doubles of LDS scratch.
 template <class Pose>
 __device__ __forceinline__ void latch_cm(const DBatch& B, const DRobot& R, DRobotState& rs, const Pose& pose, bool latch, bool eol, double* sh, int CH,
-                                         bool trace = false, int trace_index = 0)
+                                         int trace = 0, int trace_index = 0)      // (trace: StepCtl::trace, a mask)
 {
     // The sums keep the reference's order (one thread adds voxel after voxel), but only the additions are serial: the products
     // x * m are formed by the staging threads (the same single rounding), and the y / lat of getPosteriorY is taken once, of the
@@ -557,11 +592,29 @@ __device__ __forceinline__ void latch_cm(const DBatch& B, const DRobot& R, DRobo
     if (tid == 0) {
         if (latch) { const double inv = 1.0 / sm; rs.ini_cm[0] = inv * sx; rs.ini_cm[1] = inv * sy; rs.ini_cm[2] = inv * sz; rs.cm_init = 1; }
         if (eol) { const double q = miny / R.lat; rs.eol_post_y = q < 100000.0 ? q : 100000.0; }
-        if (trace) {                         // SS.CMTraceTime / SS.CMTrace: (CurTime, GetCM()) of the step just finished
+        if (trace & (1 << VXH_TRACE_LIFE)) {   // SS.CMTraceTime / SS.CMTrace: (CurTime, GetCM()) of the step just finished
             const double inv = 1.0 / sm;
             double* e = B.trace + (size_t)(R.trace_begin + trace_index) * 4;
             e[0] = rs.cur_time; e[1] = inv * sx; e[2] = inv * sy; e[3] = inv * sz;
         }
+    }
+    // <NormDistByVol> (uniform: a flag of the robot): getTotalVolume() (VX_Sim.cpp:2574-2581) of the same poses, a second pass of the same
+    // shape -- the staging threads form (scale / lat)^3, one thread adds them in voxel order.  The cube is x * x * x, each product rounded:
+    // at most an ulp per voxel from the reference's pow(x, 3), eleven orders below the six digits the result file prints.
+    if ((R.flags & RF_NORM_VOL) && trace) {
+        double vol = 0;
+        for (int c0 = 0; c0 < R.nvox; c0 += CH) {
+            for (int k = tid; k < CH && c0 + k < R.nvox; k += T) {
+                double x, y, z, scale;
+                pose(base + c0 + k, x, y, z, scale);
+                const double q = scale / R.lat;
+                sh[k] = __dmul_rn(__dmul_rn(q, q), q);
+            }
+            __syncthreads();
+            if (tid == 0) { const int n = min(CH, R.nvox - c0); for (int k = 0; k < n; ++k) vol = __dadd_rn(vol, sh[k]); }
+            __syncthreads();
+        }
+        if (tid == 0) { const double inv = 1.0 / sm; store_norm_vol_points(B, R, rs, trace, trace_index, inv * sx, inv * sy, inv * sz, vol); }
     }
 }
 

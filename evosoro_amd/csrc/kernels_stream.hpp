@@ -93,7 +93,7 @@ static __global__ __launch_bounds__(256) void k_step_begin(DBatch B, long long s
         if (c.go) actuation_sincos(R, rs.cur_time, rs.act_sin, rs.act_cos);
     }
     __syncthreads();
-    if (s_latch || s_eol || s_trace) latch_cm(B, R, rs, PoseFromState{B, rs.steps & 1}, s_latch != 0, s_eol != 0, sh, 256, s_trace != 0, s_tidx);
+    if (s_latch || s_eol || s_trace) latch_cm(B, R, rs, PoseFromState{B, rs.steps & 1}, s_latch != 0, s_eol != 0, sh, 256, s_trace, s_tidx);
 }
 
 template <int A>

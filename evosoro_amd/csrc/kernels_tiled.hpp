@@ -807,7 +807,7 @@ __global__ __launch_bounds__(VXH_TILE_THREADS) void k_tile_steps(DBatch B, const
             // ---- whole-robot passes (rare): IniCM latch / a point of the CoM trace by the robot's first tile (the others only note that
             // it happened), broad-phase
             if (K.latch || K.eol || K.trace) {
-                if (ti == T.tile0) latch_cm(B, R, rs, pose, K.latch != 0, K.eol != 0, sc, VXH_TILE_CH, K.trace != 0, K.trace_index);
+                if (ti == T.tile0) latch_cm(B, R, rs, pose, K.latch != 0, K.eol != 0, sc, VXH_TILE_CH, K.trace, K.trace_index);
                 else if (tid == 0) { if (K.latch) rs.cm_init = 1; if (K.eol) rs.eol_post_y = 1.0; }
             }
             if (!go) break;
@@ -1030,6 +1030,7 @@ __global__ __launch_bounds__(VXH_TILE_THREADS) void k_tile_steps(DBatch B, const
             g.eol_post_y = out.eol_post_y; g.act_sin = out.act_sin; g.act_cos = out.act_cos; g.act_time = out.act_time; g.maxvel2_bits = out.maxvel2_bits;
             g.steps = out.steps; g.status = out.status; g.cm_init = out.cm_init; g.active = out.active; g.diverged = out.diverged;
             g.rebuild_now = out.rebuild_now; g.rebuilds = out.rebuilds; g.col_tiled = out.col_tiled; g.ntrace = out.ntrace; g.last_trace_time = out.last_trace_time;
+            g.nxtrace[0] = out.nxtrace[0]; g.nxtrace[1] = out.nxtrace[1]; g.last_xtrace_time[0] = out.last_xtrace_time[0]; g.last_xtrace_time[1] = out.last_xtrace_time[1];
         }
     }
 }

@@ -252,13 +252,13 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void k_robot_wide(DBatch B, con
         double* const psn = ps == ps_a ? ps_b : ps_a;      // where the new poses go (the same tile without the second one)
         const FetchLds<BLOCK> fetch{ps, base};
         const int kf = __builtin_amdgcn_readfirstlane(K.flags);
-        const bool k_go = kf & 1, k_latch = kf & 2, k_eol = kf & 4, k_rebuild = (kf & 8) || reb_next, k_trace = kf & 16;
+        const bool k_go = kf & 1, k_latch = kf & 2, k_eol = kf & 4, k_rebuild = (kf & 8) || reb_next, k_trace = kf & VXH_CTL_TRACE_BITS;
         if (!k_go && !k_trace) break;
         int vv = v, vva = va;                  // opaque per-step copies (see k_robot_steps)
         asm volatile("" : "+v"(vv));
         asm volatile("" : "+v"(vva));
         if (k_latch || k_eol || k_trace)
-            fused_latch_cm<BLOCK>(R, rs, ps, rec, valid, Cl, k_latch, k_eol, k_trace, B.trace + (size_t)(R.trace_begin + K.trace_index) * 4);
+            fused_latch_cm<BLOCK>(B, R, rs, ps, rec, valid, Cl, k_latch, k_eol, fused_trace_mask(kf), K.trace_index);
         if (!k_go) break;
         if (__builtin_expect(k_rebuild, 0)) {
             fused_rebuild<BLOCK>(B, R, rs, ps, rec, 12 * BLOCK, (double*)cmask, max(0, lds_doubles - (int)((double*)cmask - lds)), vct);

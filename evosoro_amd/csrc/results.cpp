@@ -297,6 +297,15 @@ void compute_result(const RobotModel& M, const HostState& S, vxh_result* r)
         if (S.steps == 0) { ant = post = anty = posty = 0; touching = feet = 0; }   // SimState::Clear()
         r->final_dist = fd; r->norm_final_dist = fd; r->norm_frozen_dist = 0;
         r->norm_regime_dist = post - S.eol_post_y;
+        if (X.norm_dist_by_vol) {
+            // VX_SimGA.cpp:57-112: distance per trace interval over the robot's volume in it, from the traces the device recorded.  Where the
+            // reference would read element [0] of an EMPTY trace (undefined behaviour) the sum is 0.
+            const double e = X.normalization_exponent;
+            const size_t n = std::min(S.cm_trace.size() / 4, S.vol_trace.size());
+            r->norm_final_dist = norm_dist_by_vol(n, S.cm_trace.data() + 2, 4, S.vol_trace.data(), 1, lat, e);
+            if (X.afterlife_time > 0) r->norm_regime_dist = norm_dist_by_vol(S.xtrace[0].size() / 5, S.xtrace[0].data() + 2, 5, S.xtrace[0].data() + 4, 5, lat, e);
+            if (X.midlife_freeze_time > 0) r->norm_frozen_dist = norm_dist_by_vol(S.xtrace[1].size() / 5, S.xtrace[1].data() + 2, 5, S.xtrace[1].data() + 4, 5, lat, e);
+        }
         r->final_dist_y = (cm[1] - S.ini_cm[1]) / lat;
         r->anterior_dist = ant; r->posterior_dist = post; r->anterior_y = anty; r->posterior_y = posty;
         r->end_of_life_posterior_y = S.eol_post_y; r->fall_adj_post_y = S.eol_post_y;
@@ -329,6 +338,20 @@ void tag(std::string& out, const char* name, double value)
 
 const std::vector<double>& empty_trace() { static const std::vector<double> none; return none; }
 
+// the loop of VX_SimGA.cpp:59-73 (and :78-92, :97-111), operation for operation
+double norm_dist_by_vol(size_t n, const double* y, size_t y_stride, const double* vol, size_t vol_stride, double lattice_dim, double exponent)
+{
+    if (n < 2) return 0.0;
+    double last_y = y[0], last_vol = vol[0], sum = 0;
+    for (size_t i = 1; i != n; ++i) {
+        const double this_dist = (y[i * y_stride] - last_y) / lattice_dim;
+        const double this_vol = (vol[i * vol_stride] + last_vol) / 2;
+        sum += this_dist / std::pow(this_vol, exponent);
+        last_y = y[i * y_stride]; last_vol = vol[i * vol_stride];
+    }
+    return sum;
+}
+
 // <ShapeComplexityStart/End> as the reference binary prints them when it is built from its repository: computeShapeComplexity
 // (LW/VX_MeshUtil.cpp:1016-1076) writes the angle excesses to <CurvaturesTmpFile> (six significant digits each, tab-separated), runs
 // `python <base>/../curvatureEntropy.py <file>` -- a script the repository does not contain, so the call fails and the file stays as it
@@ -344,7 +367,8 @@ double shape_complexity_as_the_reference_prints_it(const RobotModel& M, const st
     return std::strtod(text, nullptr);
 }
 
-std::string result_xml(const RobotModel& M, const vxh_result& r, const std::vector<double>& cm_trace, double shape_start, double shape_end)
+std::string result_xml(const RobotModel& M, const vxh_result& r, const std::vector<double>& cm_trace, double shape_start, double shape_end,
+                       const std::vector<double>& vol_trace)
 {
     std::string out = "<?xml version=\"1.0\" ?>\n<Voxelyze_Sim_Result Version=\"1.0\">\n    <Fitness>\n";
     if (M.vxa.variant == 0) {
@@ -393,6 +417,21 @@ std::string result_xml(const RobotModel& M, const vxh_result& r, const std::vect
             out += "        </TraceStep>\n";
         }
         out += "    </CMTrace>\n";
+    }
+    if (M.vxa.variant == 0 && M.vxa.norm_dist_by_vol && M.vxa.save_traces) {            // VX_SimGA.cpp:187-198
+        out += "    <VolumeTrace>\n";
+        for (size_t i = 0; i < vol_trace.size() && 4 * i < cm_trace.size(); ++i) {      // (SS.VolTraceTime: the times of the CoM trace)
+            out += "        <TraceStep>\n";
+            const double vals[2] = {cm_trace[4 * i], vol_trace[i]};
+            static const char* vnames[2] = {"Time", "Volume"};
+            for (int k = 0; k < 2; ++k) {
+                char buf[64];
+                std::snprintf(buf, sizeof(buf), "%g", vals[k]);
+                out += "            <"; out += vnames[k]; out += ">"; out += buf; out += "</"; out += vnames[k]; out += ">\n";
+            }
+            out += "        </TraceStep>\n";
+        }
+        out += "    </VolumeTrace>\n";
     }
     out += "</Voxelyze_Sim_Result>\n";
     return out;

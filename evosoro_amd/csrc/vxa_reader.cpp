@@ -268,7 +268,15 @@ VxaModel read_vxa(const char* data, size_t len, int variant)
     m.fluid_env = flag(env, "FluidEnvironment", false);
     m.aggregate_drag_coef = num(env, "AggregateDragCoefficient", 0);
     if (variant == 0) {
-        if (flag(env, "NormDistByVol", false)) m.unsupported.push_back("NormDistByVol");
+        m.norm_dist_by_vol = flag(env, "NormDistByVol", false);
+        m.normalization_exponent = num(env, "NormalizationExponent", 1.0);
+        if (m.norm_dist_by_vol) {
+            // WriteResultFile reads element [0] of every trace it sums (VX_SimGA.cpp:61-62, :80-81, :99-100), and these settings leave one
+            // empty: without a trace interval no CoM point is ever recorded (VX_Sim.cpp:1537), and under a stop rule other than "simulation
+            // time" StopConditionValue is no time, so the after-life and frozen windows that compare CurTime with it never open
+            if (!(m.time_between_traces > 0)) m.unsupported.push_back("NormDistByVol without TimeBetweenTraces > 0");
+            if (m.stop_type != 2) m.unsupported.push_back("NormDistByVol with a StopConditionType other than 2 (simulation time)");
+        }
         if (inum(env, "NumTimeStepsInWindow", 0) > 0) m.unsupported.push_back("NumTimeStepsInWindow");
         if (flag(env, "FallingProhibited", false)) m.unsupported.push_back("FallingProhibited");
         if (flag(env, "NeedleInHaystack", false)) m.unsupported.push_back("NeedleInHaystack");

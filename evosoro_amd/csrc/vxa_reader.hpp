@@ -49,6 +49,8 @@ struct VxaModel {
     bool sticky_floor = false;
     double time_between_traces = 0;       // <TimeBetweenTraces> (VX_Environment.cpp:215), _voxcad: a point of the CoM trace at most this often
     bool save_traces = false;             // <SaveTraces> (:214): the trace is printed into the result file
+    bool norm_dist_by_vol = false;        // <NormDistByVol> (:221): distances per trace interval divided by the robot's volume over it (VX_SimGA.cpp:57-112)
+    double normalization_exponent = 1.0;  // <NormalizationExponent> (:223): ... raised to this power
     bool fluid_env = false;
     double aggregate_drag_coef = 0;
     // VXC

@@ -18,7 +18,7 @@ ROBOT_PENDING, ROBOT_FINISHED, ROBOT_DIVERGED, ROBOT_EMPTY, ROBOT_COL_OVERFLOW =
 
 EXPORTS = ["vxh_inspect_vxa_buffer", "vxh_inspect_constants", "vxh_inspect_angle_excess", "vxh_get_angle_excess", "vxh_get_mesh", "vxh_get_shape_descriptors", "vxh_plan_tiles_buffer", "vxh_convex_hull_volume", "vxh_create", "vxh_create_multi", "vxh_destroy", "vxh_add_vxa_file", "vxh_add_vxa_buffer", "vxh_add_vxa_files", "vxh_add_robots", "vxh_num_robots", "vxh_robot_dims", "vxh_voxel_actuation",
            "vxh_run", "vxh_step", "vxh_reset", "vxh_clear", "vxh_get_result", "vxh_write_result_xml",
-           "vxh_fitness_file_name", "vxh_get_state", "vxh_get_cm_trace", "vxh_get_counters", "vxh_count_bond_modes", "vxh_set_option", "vxh_strerror",
+           "vxh_fitness_file_name", "vxh_get_state", "vxh_get_cm_trace", "vxh_get_cm_trace_of", "vxh_get_volume_trace", "vxh_get_counters", "vxh_count_bond_modes", "vxh_set_option", "vxh_strerror",
            "vxh_last_error", "vxh_version", "vxh_device_count"]
 
 
@@ -139,6 +139,9 @@ def load_library():
     lib.vxh_get_state.argtypes = [P, I, P, I]
     lib.vxh_get_counters.argtypes = [P, ctypes.POINTER(VxhCounters)]
     lib.vxh_get_cm_trace.argtypes = [P, I, P, I, ctypes.POINTER(I)]
+    if hasattr(lib, "vxh_get_volume_trace"):      # (absent from earlier libraries, like the ones above)
+        lib.vxh_get_cm_trace_of.argtypes = [P, I, I, P, I, ctypes.POINTER(I)]
+        lib.vxh_get_volume_trace.argtypes = [P, I, I, P, I, ctypes.POINTER(I)]
     lib.vxh_count_bond_modes.argtypes = [P, ctypes.POINTER(LL), ctypes.POINTER(LL)]
     lib.vxh_set_option.argtypes = [P, ctypes.c_char_p, D]
     lib.vxh_strerror.argtypes = [I]
@@ -355,12 +358,25 @@ class Engine(object):
         self._check(self._lib.vxh_get_counters(self._h, ctypes.byref(out)))
         return out
 
-    def cm_trace(self, robot):
-        """[n, 4] (time, x, y, z): the centre-of-mass trace of a robot with <TimeBetweenTraces> > 0"""
+    def cm_trace(self, robot, which=0):
+        """[n, 4] (time, x, y, z): the centre-of-mass trace of a robot with <TimeBetweenTraces> > 0.  A robot with <NormDistByVol> keeps
+        three: which = 0 the life trace, 1 the after-life trace, 2 the trace of the mid-life freeze"""
         count = ctypes.c_int()
-        self._check(self._lib.vxh_get_cm_trace(self._h, robot, None, 0, ctypes.byref(count)))
+        if which == 0:
+            get = lambda out, cap: self._lib.vxh_get_cm_trace(self._h, robot, out, cap, ctypes.byref(count))
+        else:
+            get = lambda out, cap: self._lib.vxh_get_cm_trace_of(self._h, robot, which, out, cap, ctypes.byref(count))
+        self._check(get(None, 0))
         out = np.zeros((max(count.value, 1), 4), dtype=np.float64)
-        self._check(self._lib.vxh_get_cm_trace(self._h, robot, out.ctypes.data, count.value, ctypes.byref(count)))
+        self._check(get(out.ctypes.data, count.value))
+        return out[:count.value]
+
+    def volume_trace(self, robot, which=0):
+        """[n, 2] (time, volume in voxels): the robot's volume at every point of that trace (robots with <NormDistByVol>; empty otherwise)"""
+        count = ctypes.c_int()
+        self._check(self._lib.vxh_get_volume_trace(self._h, robot, which, None, 0, ctypes.byref(count)))
+        out = np.zeros((max(count.value, 1), 2), dtype=np.float64)
+        self._check(self._lib.vxh_get_volume_trace(self._h, robot, which, out.ctypes.data, count.value, ctypes.byref(count)))
         return out[:count.value]
 
     def angle_excess(self, robot, at_end=True):

@@ -70,7 +70,10 @@ def _values_from_record(pop, record, parallel):
         field = _TAG_FIELDS.get(tag.strip("<>"))
         if field is None:
             raise KeyError("objective tag %s is not a tag of the result file" % tag)
-        values[rank] = float("%.6g" % record[parallel.RECORD_FIELDS.index(field)])
+        value = record[parallel.RECORD_FIELDS.index(field)]
+        if field == "norm_final_dist":          # printed as normFinalDist - normFrozenDist (VX_SimGA.cpp:145; 0 without <NormDistByVol>)
+            value = value - record[parallel.RECORD_FIELDS.index("norm_frozen_dist")]
+        values[rank] = float("%.6g" % value)
     return values
 
 

@@ -208,6 +208,14 @@ int  vxh_get_state(const vxh_engine* e, int robot, double* out14n, int capacity)
  * recorded on the device at the end of the step in which it falls due): per point 4 doubles (time, x, y, z); count_out = points
  * recorded (may exceed capacity).  With <SaveTraces> the result XML carries the same points as <CMTrace> (VX/VX_SimGA.cpp:170-184). */
 int  vxh_get_cm_trace(const vxh_engine* e, int robot, double* out4n, int capacity, int* count_out);
+/* A _voxcad robot with <NormDistByVol>1 keeps three traces, each with the cadence of its own (VX/VX_Sim.cpp:1537-1597): `which` = 0 the life
+ * trace (CurTime > InitCmTime; what vxh_get_cm_trace returns), 1 the after-life trace (AfterlifeTime > 0 and CurTime > StopConditionValue),
+ * 2 the frozen trace (inside the MidLifeFreezeTime window).  vxh_get_cm_trace_of: per point (time, x, y, z); vxh_get_volume_trace: per
+ * point (time, getTotalVolume()), the sum over the voxels of (scale / Lattice_Dim)^3 at that step.  The Norm tags of the result are summed from
+ * them (VX/VX_SimGA.cpp:57-112), and with <SaveTraces> the result XML carries trace 0's volumes as <VolumeTrace> (:187-198).  A robot without
+ * the option has no volumes and only trace 0: count_out = 0 for the rest.  count_out may exceed capacity. */
+int  vxh_get_cm_trace_of(const vxh_engine* e, int robot, int which, double* out4n, int capacity, int* count_out);
+int  vxh_get_volume_trace(const vxh_engine* e, int robot, int which, double* out2n, int capacity, int* count_out);
 int  vxh_get_counters(const vxh_engine* e, vxh_counters* out);
 /* how many internal bonds of the batch are currently in the large-angle branch of CVXS_BondInternal::CalcLinForce
  * (VX/VXS_BondInternal.cpp:72-126, the SmallAngle flag): the two branches differ 2.5x in arithmetic, so a throughput figure

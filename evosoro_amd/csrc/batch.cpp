@@ -164,7 +164,7 @@ void lay_out_voxels(const std::vector<RobotModel>& robots, int variant, HostBatc
 }
 
 // ... the surface meshes of land_water robots
-void lay_out_meshes(const std::vector<RobotModel>& robots, int variant, HostBatch& H)
+void lay_out_meshes(const std::vector<RobotModel>& robots, int variant, const Options& opt, HostBatch& H)
 {
     const int nr = (int)robots.size(), nv = H.nv;
     H.mv_begin.assign(nr, 0);
@@ -181,6 +181,13 @@ void lay_out_meshes(const std::vector<RobotModel>& robots, int variant, HostBatc
     H.facet_vox.assign(std::max(total_facet, 1), 0); H.facet_vert.assign((size_t)3 * std::max(total_facet, 1), 0); H.facet_first.assign(H.any_mesh ? nv : 1, 0);
     H.facet_count.assign(H.any_mesh ? nv : 1, 0);
     H.facet_robot.assign(any_fluid ? std::max(total_facet, 1) : 1, 0);
+    // device_shape: the robots k_shape_results takes (a robot above its vertex cap is evaluated on the host), in batch order.  (Voxel slots
+    // are packed with the corner code into one int: a batch of 2^28 slots has no device path.)
+    if (opt.device_shape && variant == 1 && nv < (1 << 28)) {
+        for (int r = 0; r < nr; ++r)
+            if (robots[r].nmv > 0 && robots[r].nmv <= VXH_SHAPE_MAX_VERT) { H.shape_list.push_back(r); H.shape_max_nmv = std::max(H.shape_max_nmv, robots[r].nmv); }
+        if (!H.shape_list.empty()) H.shape_vert.assign((size_t)8 * total_mv, -1);
+    }
 }
 
 // ... and the class tables, exclusion rows, contact rows and wide-kernel lists
@@ -413,6 +420,11 @@ void mesh_tables(const RobotModel& M, int r, HostBatch& H)
             }
         }
         for (int k = 0; k < 3; ++k) H.vert_v0[k * tm + mv_begin + i] = M.vert_v0[(size_t)i * 3 + k];
+        if (!H.shape_vert.empty() && M.nmv <= VXH_SHAPE_MAX_VERT)
+            for (int q = 0; q < 8; ++q) {
+                const int c = M.vert_comp[(size_t)i * 8 + q];
+                if (c >= 0) H.shape_vert[(size_t)q * H.total_mv + mv_begin + i] = (base + (c >> 3)) << 3 | (c & 7);
+            }
     }
     for (int v = 0; v < M.nvox; ++v) {
         H.facet_first[base + v] = M.facet_first[v]; H.facet_count[base + v] = M.facet_count[v];
@@ -470,7 +482,7 @@ HostBatch assemble_batch(const std::vector<RobotModel>& robots, int variant, con
 {
     HostBatch H;
     lay_out_voxels(robots, variant, H);
-    lay_out_meshes(robots, variant, H);
+    lay_out_meshes(robots, variant, opt, H);
     lay_out_tables(robots, variant, opt, device_mem, H);
     // the robots are assembled on the host cores (disjoint ranges)
     const int nr = (int)robots.size();

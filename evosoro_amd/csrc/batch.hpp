@@ -61,6 +61,10 @@ struct HostBatch {
     std::vector<double> vert_v0;
     std::vector<int> facet_vox, facet_vert, facet_first, facet_robot;
     std::vector<unsigned char> facet_count;
+    // engine option device_shape, land_water robots of up to VXH_SHAPE_MAX_VERT mesh vertices: what k_shape_results reads beside the tables above
+    // (DShape, device_types.hpp) -- per mesh vertex its voxels in the host's order, and the robots it is launched for.  Empty without the option.
+    std::vector<int> shape_vert, shape_list;
+    int shape_max_nmv = 0;                     // most mesh vertices of a robot of shape_list (sizes the launch's LDS)
     // offsets of the per-robot pieces of the shared tables
     std::vector<int> vtab_off, btab_off;
     std::vector<long long> excl_off, col_off;

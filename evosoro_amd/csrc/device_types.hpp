@@ -1,5 +1,6 @@
 // Plain structs shared by host code and HIP kernels (HBM layout, see DESIGN.md "Data layout").
 #pragma once
+#include <cstddef>
 
 namespace vxh {
 
@@ -165,6 +166,30 @@ struct DResult {
     double d2max, d2min;          // max / min over the voxels of (x - IniCM.x)^2 + (y - IniCM.y)^2 (getAnteriorDist / getPosteriorDist :2584-2616)
     double ymax, ymin;            // max / min y of the voxels that are not material 5 (getAnteriorY / getPosteriorY :2620-2656)
     int touching, feet;           // voxels below the floor plane, and those of material 6 among them (GetNumTouchingFloor :2660-2712)
+};
+
+// The RobotVolume / ConvexHullVolume tags of a land_water robot, formed on the device (k_shape_results, kernels_shape.hpp; engine option
+// device_shape): [0] the rest state, [1] the final state.  fallback != 0: the kernel declined (hull_volume is then meaningless) and the
+// host evaluates the robot's four tags from the downloaded state, as without the option.
+struct DShapeResult { double robot_volume[2], hull_volume[2]; int fallback, pad; };
+// LDS of a k_shape_results workgroup for a robot of n mesh vertices, np = n rounded up to even:
+//   points  [3][np] doubles as computed + [3][np] doubles rounded to six digits                                48 B per vertex
+//   faces   fc = 2 n + VXH_SHAPE_FACE_SLACK records of 4 doubles (plane) + 3 + 3 + 1 16-bit words (vertices,
+//           neighbours, mark): a hull of n points has at most 2 n - 4 faces, the slack holds the dead ones
+//           between two compactions                                                                            46 B per face
+// n = 1024: 49152 + 2300 * 46 = 154952 B, which with the kernel's static variables (VXH_SHAPE_STATIC_LDS) fits the 160 KB (163840 B)
+// of a CU; the layout would reach to about n = 1080.  1024 covers a full 10^3 lattice (602 vertices), an 8 x 8 x 16 block (642) and every
+// robot of up to ~13^3; the 16-bit ids would allow 65534.  Robots above the cap are evaluated on the host (fallback).
+enum { VXH_SHAPE_THREADS = 256, VXH_SHAPE_MAX_VERT = 1024, VXH_SHAPE_FACE_SLACK = 252, VXH_SHAPE_STATIC_LDS = 512 };
+VXH_HD inline int shape_face_cap(int nmv) { return 2 * nmv + VXH_SHAPE_FACE_SLACK; }
+VXH_HD inline size_t shape_lds_bytes(int nmv) { return (size_t)48 * ((nmv + 1) & ~1) + (size_t)46 * shape_face_cap(nmv); }
+// what k_shape_results reads beside the batch (uploaded when the option is on; the batch itself is the same with and without it)
+struct DShape {
+    const int* list;              // the robots it evaluates, one workgroup each
+    const int* vert;              // [8][total_mv] per mesh vertex the voxels sharing it IN THE HOST'S ORDER (RobotModel::vert_comp, voxel order):
+                                  // global voxel slot << 3 | corner code, -1 behind the last
+    const double* nom;            // [3][nv] nominal positions: the rest state
+    DShapeResult* out;            // [n_robots]
 };
 
 // (collision partners per surface voxel: DRobot::col_cap; a row that would need more -> VXH_ROBOT_COL_OVERFLOW)

@@ -104,6 +104,12 @@ struct Engine::Device {
     hipEvent_t tile_t0 = nullptr, tile_t1 = nullptr;
     int n_cu = 0;
     DResult* results = nullptr;               // [robots] output of k_results (freed with the batch)
+    // engine option device_shape: what k_shape_results reads and writes (uploaded behind everything else: a batch without the option is laid out
+    // as it always was), the robots it is launched for, the LDS of the largest
+    DShape shape{};
+    int n_shape = 0;
+    size_t shape_lds = 0;
+    std::vector<unsigned char> shape_listed;  // per robot
     DRobotState* h_rstate = nullptr;          // pinned host mirror of DBatch::rstate: copied back on the call's own stream, behind its kernels
     size_t h_rstate_cap = 0;
     // a call that has been launched and not yet waited for (advance_launch / advance_finish)
@@ -203,6 +209,7 @@ struct Engine::Device {
         alloc_bytes.clear();
         dbg_uploads.clear();
         results = nullptr;
+        shape = DShape{}; n_shape = 0;
         B = DBatch{};
     }
     ~Device()                             // (the owner has made the device current)
@@ -393,6 +400,7 @@ const OptionDesc option_table[] = {
     {"shape_descriptors", &Options::shape_descriptors, OptionDesc::FLAG, OptionDesc::WHOLE, 0, 1,      false, false},      // (robots added FROM NOW ON carry the surface mesh)
     {"host_results",      &Options::host_results,      OptionDesc::FLAG, OptionDesc::ANY,   0, 0,      false, false},
     {"dispatch_order",    &Options::dispatch_order,    OptionDesc::FLAG, OptionDesc::WHOLE, 0, 1,      false, false},
+    {"device_shape",      &Options::device_shape,      OptionDesc::FLAG, OptionDesc::WHOLE, 0, 1,      true,  false},
 };
 const OptionDesc& find_option(const std::string& key)
 {
@@ -594,6 +602,18 @@ void Engine::prepare()
 #ifdef VXH_PHASE_TIMING
     B.prof = D.alloc_zero<unsigned long long>(VXH_PROF_WORDS);
 #endif
+    D.n_shape = (int)H.shape_list.size();
+    D.shape_listed.assign(nr, 0);
+    if (D.n_shape > 0) {
+        for (int r : H.shape_list) D.shape_listed[r] = 1;
+        D.shape.list = D.upload(H.shape_list);
+        D.shape.vert = D.upload(H.shape_vert);
+        double* nom = D.alloc_raw<double>((size_t)3 * nv);      // the rest state: planes 0..2 of vs as they were uploaded above
+        HIP_OK(hipMemcpyAsync(nom, B.vs, sizeof(double) * 3 * nv, hipMemcpyDeviceToDevice, D.stream));
+        D.shape.nom = nom;
+        D.shape.out = D.alloc_zero<DShapeResult>(nr);
+        D.shape_lds = shape_lds_bytes(H.shape_max_nmv);
+    }
     B.small_angle_w = std::cos(VXH_SMALL_ANGLE_RAD * 0.5);                    // Vec3D.h:55-59
     B.smallish_angle_w = std::cos(VXH_HYST * VXH_SMALL_ANGLE_RAD * 0.5);
     B.slthresh_acos2sqrt = 1.0 - 0.9988 * 0.9988;
@@ -1023,9 +1043,18 @@ void Engine::download_reduced()
         HIP_OK(hipGetLastError());
         std::vector<DResult> h(nr);
         HIP_OK(hipMemcpyAsync(h.data(), D.results, sizeof(DResult) * nr, hipMemcpyDeviceToHost, D.stream));
+        std::vector<DShapeResult> hs;
+        if (D.n_shape > 0) {               // land_water under device_shape: the volume tags of the rest state and of this state
+            launch_shape_results(D.B, D.shape, D.n_shape, D.shape_lds, D.stream);
+            HIP_OK(hipGetLastError());
+            hs.resize(nr);
+            HIP_OK(hipMemcpyAsync(hs.data(), D.shape.out, sizeof(DShapeResult) * nr, hipMemcpyDeviceToHost, D.stream));
+        }
         HIP_OK(hipStreamSynchronize(D.stream));
         for (int r = 0; r < nr; ++r) {
             HostState& H = host_[r];
+            H.shape_fallback = hs.empty() || !D.shape_listed[r] || hs[r].fallback != 0;
+            if (!H.shape_fallback) for (int k = 0; k < 2; ++k) { H.dev_robot_volume[k] = hs[r].robot_volume[k]; H.dev_hull_volume[k] = hs[r].hull_volume[k]; }
             H.reduced = true;
             for (int k = 0; k < 3; ++k) H.red_cm[k] = h[r].cm[k];
             H.d2max = h[r].d2max; H.d2min = h[r].d2min; H.ymax = h[r].ymax; H.ymin = h[r].ymin; H.touching = h[r].touching; H.feet = h[r].feet;
@@ -1055,12 +1084,20 @@ void Engine::result(int robot, vxh_result* out)
 {
     if (!prepared_) throw std::logic_error("results requested before vxh_run/vxh_step");
     // _voxcad: every tag from the device-side reductions; land_water: the RobotVolume tags need the surface mesh of the final state
-    // (poses + strains of every voxel), evaluated on the host
-    const bool need_state = variant_ == 1 || opt_.host_results;
+    // (poses + strains of every voxel), evaluated on the host -- or, under the option device_shape, by k_shape_results; a robot that
+    // kernel declines (above its vertex cap, degenerate) has the state downloaded for it on demand and is evaluated the old way
+    const bool dev_shape = variant_ == 1 && opt_.device_shape && !opt_.host_results;
+    const bool need_state = (variant_ == 1 && !dev_shape) || opt_.host_results;
     if (need_state && !state_downloaded_) download();
     if (!need_state && !reduced_downloaded_) download_reduced();
     if (variant_ == 0 && robots_[robot].vxa.norm_dist_by_vol && !reduced_downloaded_) download_reduced();   // (the traces the Norm tags are summed from)
     HostState& H = host_[robot];
+    if (dev_shape && H.shape_fallback && robots_[robot].nmv > 0) {
+        if (!state_downloaded_) download();
+        compute_result(robots_[robot], H, out);
+        out->reserved = 1;
+        return;
+    }
     if (need_state) { const bool keep = H.reduced; H.reduced = false; compute_result(robots_[robot], H, out); H.reduced = keep; }
     else compute_result(robots_[robot], H, out);
 }

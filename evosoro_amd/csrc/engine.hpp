@@ -23,6 +23,10 @@ struct HostState {                      // final/current state of one robot, dow
     bool reduced = false;
     double red_cm[3] = {0, 0, 0}, d2max = 0, d2min = 0, ymax = 0, ymin = 0;
     int touching = 0, feet = 0;
+    // land_water, engine option device_shape: RobotVolume / ConvexHullVolume [0] Start, [1] End from k_shape_results; shape_fallback: the kernel
+    // declined this robot (or was not launched for it) and the four tags come from the downloaded state
+    double dev_robot_volume[2] = {0, 0}, dev_hull_volume[2] = {0, 0};
+    bool shape_fallback = true;
     std::vector<double> cm_trace;                              // [4*k] (time, x, y, z): SS.CMTraceTime / SS.CMTrace
     // robots with <NormDistByVol>: SS.VolTrace, a volume per point of cm_trace, and the after-life [0] / frozen [1] traces,
     // [5*k] (time, x, y, z, volume): SS.CMTraceAfterLife + SS.VolTraceAfterLife, SS.CMTraceWhileFrozen + SS.VolTraceWhileFrozen
@@ -53,6 +57,8 @@ struct Options {
                                                // stepped by the MESH kernel variants, which record the directional strains the final mesh needs
     int host_results = 0;                      // every result from the downloaded voxel state on the host (cross-check)
     int dispatch_order = 1;                    // resident kernel: the workgroups of a launch by measured cost, longest first (dispatch_order.hpp); 0: the list order
+    int device_shape = 0;                      // land_water: the RobotVolume / ConvexHullVolume tags from k_shape_results (kernels_shape.hpp) instead of from the
+                                               // downloaded voxel state; a robot the kernel declines is evaluated on the host as before
 };
 
 class Engine {

@@ -1,5 +1,5 @@
 // Host-side launch entry points of every kernel.  Each kernel family is its own translation unit (launch_fused_*.hip,
-// launch_wide.hip, launch_tiled.hip, launch_stream.hip) so that the Makefile compiles them side by side and a change to one family
+// launch_wide.hip, launch_tiled.hip, launch_stream.hip, launch_shape.hip) so that the Makefile compiles them side by side and a change to one family
 // recompiles that family only; engine.hip (device memory, the call loop, graph capture) compiles no kernel and sees these declarations.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -50,6 +50,8 @@ void launch_stream_round(const DBatch& B, bool any_fluid, int reb_blocks, const 
 void launch_stream_finish(const DBatch& B, hipStream_t s, long long cap);
 // k_results: one DResult per robot
 void launch_results(const DBatch& B, int n_robots, DResult* out, hipStream_t s);
+// k_shape_results (kernels_shape.hpp): one workgroup per robot of Q.list (count of them); lds: shape_lds_bytes of the largest
+void launch_shape_results(const DBatch& B, const DShape& Q, int count, size_t lds, hipStream_t s);
 // k_dispatch_order (kernels_order.hpp): perm = the `count` list entries by descending expected cost of a launch of `len` steps (0: the list order)
 void launch_dispatch_order(const DispatchCost* cost, int count, int len, int* perm, hipStream_t s);
 

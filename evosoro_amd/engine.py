@@ -2,6 +2,9 @@
 
 There is no fallback: if the shared library is missing or no HIP device is usable this module raises —
 the product path never routes through a CPU implementation.
+
+Engine options (Engine.set_option, documented in include/vxhip.h) pass through by name; among them "device_shape": 1 = the volume and
+convex-hull tags of land_water robots come from the device and result() no longer downloads the voxel state (default 0).
 """
 import ctypes
 import os

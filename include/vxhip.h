@@ -68,7 +68,7 @@ typedef struct vxh_result {
     double norm_abs_disp, norm_dist_x, norm_dist_y, norm_dist_z;
     double robot_volume_start, robot_volume_end;   /* <RobotVolumeStart/End>, LW/VX_MeshUtil.cpp:908-952 */
     int col_rebuilds;      /* diagnostic: how often CalcL1Bonds ran (VX/VX_Sim.cpp:1741-1747) */
-    int reserved;
+    int reserved;          /* bit 0: option "device_shape" is on and the four volume tags of this robot were evaluated on the host all the same */
     double hull_volume_start, hull_volume_end;     /* <ConvexHullVolumeStart/End>: convex hull of the surface-mesh vertices, which the
                                                       reference gets from an external qhull (LW/VX_MeshUtil.cpp:775-900); the
                                                       <ShapeComplexity*> tags: see vxh_get_angle_excess */
@@ -258,7 +258,13 @@ int  vxh_count_bond_modes(const vxh_engine* e, long long* large_angle_out, long 
  *   "dispatch_order"    1 (default) = the workgroups of a resident-kernel launch of more than 128 steps take the robots by what the
  *                       previous launch measured them to cost, longest first, so that the CUs finish together (shorter launches: the
  *                       robots due for a collision broad-phase run first); 0 = in the order of the host's list (A/B runs, tests).
- *                       The robots do not interact: the same results, bit for bit, either way.  May be changed at any time. */
+ *                       The robots do not interact: the same results, bit for bit, either way.  May be changed at any time.
+ *   "device_shape"      1 = the <RobotVolumeStart/End> and <ConvexHullVolumeStart/End> tags of land_water robots are formed on the device
+ *                       (k_shape_results: the same mesh vertices and the same hull faces as the host routines, the two volumes summed in
+ *                       another order -- they agree with the host's to ~1e-15 relative, not to the bit), and vxh_get_result no longer
+ *                       downloads the voxel state.  A robot the kernel declines -- more than 1024 mesh vertices, a degenerate point set --
+ *                       is evaluated on the host as with 0, and bit 0 of vxh_result.reserved says so.  Belongs to the uploaded batch like
+ *                       "tiled" .. "fused": set it before the first vxh_run / vxh_step.  Default 0. */
 int  vxh_set_option(vxh_engine* e, const char* key, double value);
 
 const char* vxh_strerror(int status);

@@ -184,9 +184,16 @@ void lay_out_meshes(const std::vector<RobotModel>& robots, int variant, const Op
     // device_shape: the robots k_shape_results takes (a robot above its vertex cap is evaluated on the host), in batch order.  (Voxel slots
     // are packed with the corner code into one int: a batch of 2^28 slots has no device path.)
     if (opt.device_shape && variant == 1 && nv < (1 << 28)) {
-        for (int r = 0; r < nr; ++r)
-            if (robots[r].nmv > 0 && robots[r].nmv <= VXH_SHAPE_MAX_VERT) { H.shape_list.push_back(r); H.shape_max_nmv = std::max(H.shape_max_nmv, robots[r].nmv); }
-        if (!H.shape_list.empty()) H.shape_vert.assign((size_t)8 * total_mv, -1);
+        for (int r = 0; r < nr; ++r) {
+            const int n = robots[r].nmv;
+            if (n > 0 && n <= VXH_SHAPE_MAX_VERT) { H.shape_list.push_back(r); H.shape_max_nmv = std::max(H.shape_max_nmv, n); }
+            else if (opt.device_shape_large && n > VXH_SHAPE_MAX_VERT && n <= VXH_SHAPE_LARGE_MAX_VERT) {      // k_shape_results_large
+                H.shape_large_list.push_back(r); H.shape_large_off.push_back(H.shape_large_points);
+                H.shape_large_points += (long long)6 * n;
+                H.shape_large_lds = std::max(H.shape_large_lds, shape_large_lds_bytes(n));
+            }
+        }
+        if (!H.shape_list.empty() || !H.shape_large_list.empty()) H.shape_vert.assign((size_t)8 * total_mv, -1);
     }
 }
 
@@ -402,6 +409,8 @@ void mesh_tables(const RobotModel& M, int r, HostBatch& H)
     }
     if (M.nmv == 0) return;
     const size_t tm = (size_t)std::max(H.total_mv, 1);
+    // (a robot of either shape kernel's list; both lists are in batch order)
+    const bool shape_listed = !H.shape_vert.empty() && (M.nmv <= VXH_SHAPE_MAX_VERT || std::binary_search(H.shape_large_list.begin(), H.shape_large_list.end(), r));
     for (int i = 0; i < M.nmv; ++i) {
         unsigned w[3] = {0, 0, 0};
         for (int q = 0; q < 8; ++q) {
@@ -420,7 +429,7 @@ void mesh_tables(const RobotModel& M, int r, HostBatch& H)
             }
         }
         for (int k = 0; k < 3; ++k) H.vert_v0[k * tm + mv_begin + i] = M.vert_v0[(size_t)i * 3 + k];
-        if (!H.shape_vert.empty() && M.nmv <= VXH_SHAPE_MAX_VERT)
+        if (shape_listed)
             for (int q = 0; q < 8; ++q) {
                 const int c = M.vert_comp[(size_t)i * 8 + q];
                 if (c >= 0) H.shape_vert[(size_t)q * H.total_mv + mv_begin + i] = (base + (c >> 3)) << 3 | (c & 7);

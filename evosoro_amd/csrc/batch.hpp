@@ -65,6 +65,13 @@ struct HostBatch {
     // (DShape, device_types.hpp) -- per mesh vertex its voxels in the host's order, and the robots it is launched for.  Empty without the option.
     std::vector<int> shape_vert, shape_list;
     int shape_max_nmv = 0;                     // most mesh vertices of a robot of shape_list (sizes the launch's LDS)
+    // ... and option device_shape_large: the robots above that cap, up to VXH_SHAPE_LARGE_MAX_VERT vertices, that k_shape_results_large takes
+    // (shape_vert is filled for them too), per list entry the first double of its 6 nmv of the point table, the table's size in
+    // doubles, and the most LDS a robot of the list needs (shape_large_lds_bytes is not monotonic in nmv: the launch takes the maximum)
+    std::vector<int> shape_large_list;
+    std::vector<long long> shape_large_off;
+    long long shape_large_points = 0;
+    size_t shape_large_lds = 0;
     // offsets of the per-robot pieces of the shared tables
     std::vector<int> vtab_off, btab_off;
     std::vector<long long> excl_off, col_off;

@@ -183,13 +183,37 @@ struct DShapeResult { double robot_volume[2], hull_volume[2]; int fallback, pad;
 enum { VXH_SHAPE_THREADS = 256, VXH_SHAPE_MAX_VERT = 1024, VXH_SHAPE_FACE_SLACK = 252, VXH_SHAPE_STATIC_LDS = 512 };
 VXH_HD inline int shape_face_cap(int nmv) { return 2 * nmv + VXH_SHAPE_FACE_SLACK; }
 VXH_HD inline size_t shape_lds_bytes(int nmv) { return (size_t)48 * ((nmv + 1) & ~1) + (size_t)46 * shape_face_cap(nmv); }
-// what k_shape_results reads beside the batch (uploaded when the option is on; the batch itself is the same with and without it)
+// k_shape_results_large (kernels_shape_large.hpp; engine option device_shape_large): robots of VXH_SHAPE_MAX_VERT < n <=
+// VXH_SHAPE_LARGE_MAX_VERT mesh vertices.  The points live in a table in HBM (DShape::large_pts), LDS holds the hull alone:
+//   ring    two blocks of T = VXH_SHAPE_LARGE_THREADS points, 3 doubles each                                   48 T B
+//   vertex  one 16-bit cone-linking word per mesh vertex, np = n rounded up to a multiple of 4                  2 B per vertex
+//   faces   the records of k_shape_results, 46 B each: as many as the rest of the CU's 163840 B holds once the kernel's static
+//           variables (VXH_SHAPE_LARGE_STATIC_LDS) are taken off.  NOT 2 n + slack: a hull of more vertices than half of that
+//           overflows the list even after compaction, and the robot falls back to the host.
+// T = 256, n = 1178 (a full 14^3): 163840 - 1024 - 12288 - 2360 = 148168 B -> 3220 faces (even), a hull of up to 1612 vertices: every mesh
+// of up to 1612 vertices fits whatever its shape.  n = 8192: 163840 - 1024 - 12288 - 16384 = 134144 B -> 2916 faces, a hull of up to
+// 1460 of the 8192 vertices.  The cap is 8192: ids are 16 bits with SHAPE_NONE reserved (65534 would be the limit of the format), but
+// each further vertex costs its word, and beyond 8192 the face list (2916) could no longer hold the hull of a mesh a sixth of whose
+// vertices are hull vertices.  The face capacity is a function of the robot's n alone (never of the batch): so is the order of the faces.
+enum { VXH_SHAPE_LARGE_THREADS = 256, VXH_SHAPE_LARGE_MAX_VERT = 8192, VXH_SHAPE_LARGE_STATIC_LDS = 1024, VXH_SHAPE_CU_LDS = 163840 };
+VXH_HD inline int shape_large_face_cap(int nmv)
+{
+    return (VXH_SHAPE_CU_LDS - VXH_SHAPE_LARGE_STATIC_LDS - 48 * VXH_SHAPE_LARGE_THREADS - 2 * ((nmv + 3) & ~3)) / 46 & ~1;
+}
+VXH_HD inline size_t shape_large_lds_bytes(int nmv) { return (size_t)48 * VXH_SHAPE_LARGE_THREADS + (size_t)2 * ((nmv + 3) & ~3) + (size_t)46 * shape_large_face_cap(nmv); }
+// what the shape kernels read beside the batch (uploaded when the option is on; the batch itself is the same with and without it)
 struct DShape {
-    const int* list;              // the robots it evaluates, one workgroup each
+    const int* list;              // the robots k_shape_results evaluates, one workgroup each
     const int* vert;              // [8][total_mv] per mesh vertex the voxels sharing it IN THE HOST'S ORDER (RobotModel::vert_comp, voxel order):
                                   // global voxel slot << 3 | corner code, -1 behind the last
     const double* nom;            // [3][nv] nominal positions: the rest state
     DShapeResult* out;            // [n_robots]
+    // device_shape_large: the robots of k_shape_results_large, per list entry the first double of its range of the point table, and the
+    // table -- [6][nmv] per robot: the vertices as computed (x, y, z), then rounded to six digits (x, y, z); written and read by that
+    // robot's workgroup alone.  All null without the option.
+    const int* large_list;
+    const long long* large_off;
+    double* large_pts;
 };
 
 // (collision partners per surface voxel: DRobot::col_cap; a row that would need more -> VXH_ROBOT_COL_OVERFLOW)

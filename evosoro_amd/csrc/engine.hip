@@ -107,8 +107,8 @@ struct Engine::Device {
     // engine option device_shape: what k_shape_results reads and writes (uploaded behind everything else: a batch without the option is laid out
     // as it always was), the robots it is launched for, the LDS of the largest
     DShape shape{};
-    int n_shape = 0;
-    size_t shape_lds = 0;
+    int n_shape = 0, n_shape_large = 0;       // (the second: robots of k_shape_results_large, option device_shape_large)
+    size_t shape_lds = 0, shape_large_lds = 0;
     std::vector<unsigned char> shape_listed;  // per robot
     DRobotState* h_rstate = nullptr;          // pinned host mirror of DBatch::rstate: copied back on the call's own stream, behind its kernels
     size_t h_rstate_cap = 0;
@@ -209,7 +209,7 @@ struct Engine::Device {
         alloc_bytes.clear();
         dbg_uploads.clear();
         results = nullptr;
-        shape = DShape{}; n_shape = 0;
+        shape = DShape{}; n_shape = n_shape_large = 0;
         B = DBatch{};
     }
     ~Device()                             // (the owner has made the device current)
@@ -401,6 +401,7 @@ const OptionDesc option_table[] = {
     {"host_results",      &Options::host_results,      OptionDesc::FLAG, OptionDesc::ANY,   0, 0,      false, false},
     {"dispatch_order",    &Options::dispatch_order,    OptionDesc::FLAG, OptionDesc::WHOLE, 0, 1,      false, false},
     {"device_shape",      &Options::device_shape,      OptionDesc::FLAG, OptionDesc::WHOLE, 0, 1,      true,  false},
+    {"device_shape_large", &Options::device_shape_large, OptionDesc::FLAG, OptionDesc::WHOLE, 0, 1,    true,  false},
 };
 const OptionDesc& find_option(const std::string& key)
 {
@@ -603,8 +604,9 @@ void Engine::prepare()
     B.prof = D.alloc_zero<unsigned long long>(VXH_PROF_WORDS);
 #endif
     D.n_shape = (int)H.shape_list.size();
+    D.n_shape_large = (int)H.shape_large_list.size();
     D.shape_listed.assign(nr, 0);
-    if (D.n_shape > 0) {
+    if (D.n_shape > 0 || D.n_shape_large > 0) {
         for (int r : H.shape_list) D.shape_listed[r] = 1;
         D.shape.list = D.upload(H.shape_list);
         D.shape.vert = D.upload(H.shape_vert);
@@ -613,6 +615,13 @@ void Engine::prepare()
         D.shape.nom = nom;
         D.shape.out = D.alloc_zero<DShapeResult>(nr);
         D.shape_lds = shape_lds_bytes(H.shape_max_nmv);
+    }
+    if (D.n_shape_large > 0) {             // device_shape_large: the second list and the point table of k_shape_results_large
+        for (int r : H.shape_large_list) D.shape_listed[r] = 1;
+        D.shape.large_list = D.upload(H.shape_large_list);
+        D.shape.large_off = D.upload(H.shape_large_off);
+        D.shape.large_pts = D.alloc_raw<double>((size_t)H.shape_large_points);
+        D.shape_large_lds = H.shape_large_lds;
     }
     B.small_angle_w = std::cos(VXH_SMALL_ANGLE_RAD * 0.5);                    // Vec3D.h:55-59
     B.smallish_angle_w = std::cos(VXH_HYST * VXH_SMALL_ANGLE_RAD * 0.5);
@@ -1044,8 +1053,9 @@ void Engine::download_reduced()
         std::vector<DResult> h(nr);
         HIP_OK(hipMemcpyAsync(h.data(), D.results, sizeof(DResult) * nr, hipMemcpyDeviceToHost, D.stream));
         std::vector<DShapeResult> hs;
-        if (D.n_shape > 0) {               // land_water under device_shape: the volume tags of the rest state and of this state
-            launch_shape_results(D.B, D.shape, D.n_shape, D.shape_lds, D.stream);
+        if (D.n_shape > 0 || D.n_shape_large > 0) {      // land_water under device_shape: the volume tags of the rest state and of this state
+            if (D.n_shape > 0) launch_shape_results(D.B, D.shape, D.n_shape, D.shape_lds, D.stream);
+            if (D.n_shape_large > 0) launch_shape_results_large(D.B, D.shape, D.n_shape_large, D.shape_large_lds, D.stream);
             HIP_OK(hipGetLastError());
             hs.resize(nr);
             HIP_OK(hipMemcpyAsync(hs.data(), D.shape.out, sizeof(DShapeResult) * nr, hipMemcpyDeviceToHost, D.stream));

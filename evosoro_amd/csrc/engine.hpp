@@ -59,6 +59,8 @@ struct Options {
     int dispatch_order = 1;                    // resident kernel: the workgroups of a launch by measured cost, longest first (dispatch_order.hpp); 0: the list order
     int device_shape = 0;                      // land_water: the RobotVolume / ConvexHullVolume tags from k_shape_results (kernels_shape.hpp) instead of from the
                                                // downloaded voxel state; a robot the kernel declines is evaluated on the host as before
+    int device_shape_large = 0;                // ... and, with device_shape, robots of more than VXH_SHAPE_MAX_VERT (up to VXH_SHAPE_LARGE_MAX_VERT) mesh
+                                               // vertices by k_shape_results_large (kernels_shape_large.hpp) instead of on the host
 };
 
 class Engine {

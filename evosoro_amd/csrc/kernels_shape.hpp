@@ -22,14 +22,16 @@ namespace vxh {
 
 enum : unsigned short { SHAPE_NONE = 0xFFFFu };      // a dead face (in its first vertex) / a neighbour not linked yet
 
-struct ShapeShared {              // static LDS of the workgroup
-    double red[4];
-    double best_v[4];
-    int best_i[4];
-    int scan[4];
+template <int NW>                 // NW wavefronts: k_shape_results has four, k_shape_results_large (kernels_shape_large.hpp) its own count
+struct ShapeSharedN {             // static LDS of the workgroup
+    double red[NW];
+    double best_v[NW];
+    int best_i[NW];
+    int scan[NW];
     int any[3];                   // "some lane sees a face" of the current point, rotating (one barrier per point)
     int bad;                      // the pass cannot go on: capacity, a horizon that does not close
 };
+typedef ShapeSharedN<VXH_SHAPE_THREADS / 64> ShapeShared;
 
 struct ShapeLds {
     double *raw, *pt, *plane;
@@ -38,27 +40,35 @@ struct ShapeLds {
     int np, fc;
 };
 
-// fixed-shape reductions over the 256 threads: butterfly inside a wavefront (every lane ends with the same bits: the operands of each
-// level commute), then the four wavefronts as (0 + 1) + (2 + 3)
-__device__ __forceinline__ double shape_block_sum(double v, ShapeShared& S, int tid)
+// fixed-shape reductions over the workgroup: butterfly inside a wavefront (every lane ends with the same bits: the operands of each
+// level commute), then the wavefronts as a fixed pairwise tree -- four of them: (0 + 1) + (2 + 3)
+template <int NW>
+__device__ __forceinline__ double shape_block_sum(double v, ShapeSharedN<NW>& S, int tid)
 {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off);
     if ((tid & 63) == 0) S.red[tid >> 6] = v;
     __syncthreads();
-    const double t = (S.red[0] + S.red[1]) + (S.red[2] + S.red[3]);
+    double t[NW];
+#pragma unroll
+    for (int w = 0; w < NW; ++w) t[w] = S.red[w];
+#pragma unroll
+    for (int s = 1; s < NW; s <<= 1)
+#pragma unroll
+        for (int w = 0; w < NW; w += 2 * s) t[w] = t[w] + t[w + s];
     __syncthreads();
-    return t;
+    return t[0];
 }
 
-__device__ __forceinline__ double shape_block_max(double v, ShapeShared& S, int tid)
+template <int NW>
+__device__ __forceinline__ double shape_block_max(double v, ShapeSharedN<NW>& S, int tid)
 {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_xor(v, off); v = o > v ? o : v; }
     if ((tid & 63) == 0) S.red[tid >> 6] = v;
     __syncthreads();
     double t = S.red[0];
-    for (int w = 1; w < 4; ++w) t = S.red[w] > t ? S.red[w] : t;
+    for (int w = 1; w < NW; ++w) t = S.red[w] > t ? S.red[w] : t;
     __syncthreads();
     return t;
 }
@@ -71,20 +81,22 @@ __device__ __forceinline__ ShapeBest shape_better(ShapeBest a, ShapeBest b)
     if (a.i < 0) return b;
     return (b.v > a.v || (b.v == a.v && b.i < a.i)) ? b : a;
 }
-__device__ __forceinline__ ShapeBest shape_block_best(ShapeBest b, ShapeShared& S, int tid)
+template <int NW>
+__device__ __forceinline__ ShapeBest shape_block_best(ShapeBest b, ShapeSharedN<NW>& S, int tid)
 {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) { ShapeBest o; o.v = __shfl_xor(b.v, off); o.i = __shfl_xor(b.i, off); b = shape_better(b, o); }
     if ((tid & 63) == 0) { S.best_v[tid >> 6] = b.v; S.best_i[tid >> 6] = b.i; }
     __syncthreads();
     ShapeBest t; t.v = S.best_v[0]; t.i = S.best_i[0];
-    for (int w = 1; w < 4; ++w) { ShapeBest o; o.v = S.best_v[w]; o.i = S.best_i[w]; t = shape_better(t, o); }
+    for (int w = 1; w < NW; ++w) { ShapeBest o; o.v = S.best_v[w]; o.i = S.best_i[w]; t = shape_better(t, o); }
     __syncthreads();
     return t;
 }
 
 // exclusive prefix sum of one int per thread, in thread order; total: the sum
-__device__ __forceinline__ int shape_block_scan(int c, int& total, ShapeShared& S, int tid)
+template <int NW>
+__device__ __forceinline__ int shape_block_scan(int c, int& total, ShapeSharedN<NW>& S, int tid)
 {
     const int lane = tid & 63, w = tid >> 6;
     int inc = c;
@@ -94,7 +106,8 @@ __device__ __forceinline__ int shape_block_scan(int c, int& total, ShapeShared& 
     __syncthreads();
     int base = 0;
     for (int k = 0; k < w; ++k) base += S.scan[k];
-    total = S.scan[0] + S.scan[1] + S.scan[2] + S.scan[3];
+    total = S.scan[0];
+    for (int k = 1; k < NW; ++k) total += S.scan[k];
     __syncthreads();
     return base + inc - c;
 }
@@ -153,11 +166,12 @@ __device__ __forceinline__ void shape_put_face(const ShapeLds& L, int s, int a, 
 }
 
 // Dead faces out of the list, in place, order kept; returns the new length.  The new index of every live face goes into its mark, then
-// the list moves tile by tile (256 faces: read, barrier, write -- a face only ever moves down, into slots whose faces have been read).
-__device__ inline int shape_compact(const ShapeLds& L, int nf, ShapeShared& S, int tid)
+// the list moves tile by tile (one face per thread: read, barrier, write -- a face only ever moves down, into slots whose faces have been read).
+template <int NW>
+__device__ inline int shape_compact(const ShapeLds& L, int nf, ShapeSharedN<NW>& S, int tid)
 {
     int live = 0;
-    for (int t0 = 0; t0 < nf; t0 += VXH_SHAPE_THREADS) {
+    for (int t0 = 0; t0 < nf; t0 += 64 * NW) {
         const int f = t0 + tid;
         const int alive = (f < nf && L.fv[f] != SHAPE_NONE) ? 1 : 0;
         int total;
@@ -166,7 +180,7 @@ __device__ inline int shape_compact(const ShapeLds& L, int nf, ShapeShared& S, i
         live += total;
     }
     __syncthreads();
-    for (int t0 = 0; t0 < nf; t0 += VXH_SHAPE_THREADS) {
+    for (int t0 = 0; t0 < nf; t0 += 64 * NW) {
         const int f = t0 + tid;
         const bool alive = f < nf && L.fv[f] != SHAPE_NONE;
         double pl[4] = {0, 0, 0, 0};

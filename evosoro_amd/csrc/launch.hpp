@@ -52,6 +52,8 @@ void launch_stream_finish(const DBatch& B, hipStream_t s, long long cap);
 void launch_results(const DBatch& B, int n_robots, DResult* out, hipStream_t s);
 // k_shape_results (kernels_shape.hpp): one workgroup per robot of Q.list (count of them); lds: shape_lds_bytes of the largest
 void launch_shape_results(const DBatch& B, const DShape& Q, int count, size_t lds, hipStream_t s);
+// k_shape_results_large (kernels_shape_large.hpp): one workgroup per robot of Q.large_list; lds: the most shape_large_lds_bytes of them
+void launch_shape_results_large(const DBatch& B, const DShape& Q, int count, size_t lds, hipStream_t s);
 // k_dispatch_order (kernels_order.hpp): perm = the `count` list entries by descending expected cost of a launch of `len` steps (0: the list order)
 void launch_dispatch_order(const DispatchCost* cost, int count, int len, int* perm, hipStream_t s);
 

@@ -264,7 +264,12 @@ int  vxh_count_bond_modes(const vxh_engine* e, long long* large_angle_out, long 
  *                       another order -- they agree with the host's to ~1e-15 relative, not to the bit), and vxh_get_result no longer
  *                       downloads the voxel state.  A robot the kernel declines -- more than 1024 mesh vertices, a degenerate point set --
  *                       is evaluated on the host as with 0, and bit 0 of vxh_result.reserved says so.  Belongs to the uploaded batch like
- *                       "tiled" .. "fused": set it before the first vxh_run / vxh_step.  Default 0. */
+ *                       "tiled" .. "fused": set it before the first vxh_run / vxh_step.  Default 0.
+ *   "device_shape_large" 1 = with "device_shape", robots of 1025 to 8192 mesh vertices are evaluated on the device too, by a second kernel
+ *                       (k_shape_results_large: points in device memory, the hull in LDS; same agreement with the host).  Its face
+ *                       list holds about 3000 faces: a robot whose hull has more vertices than about 1500 is declined like a
+ *                       degenerate one (host, bit 0 of reserved).  No effect without "device_shape"; robots of up to 1024 vertices are
+ *                       evaluated exactly as without it.  Set it before the first vxh_run / vxh_step.  Default 0. */
 int  vxh_set_option(vxh_engine* e, const char* key, double value);
 
 const char* vxh_strerror(int status);

@@ -1481,3 +1481,25 @@ if __name__ == "__main__" and "swimtiles" in sys.argv[1:]:
     _window(engine.VOXCAD, walkers, Env(), {}, 300, 1000, tag="64 x 8^3 walkers", label="swimtiles")
     for k in (2, 4):
         _window(engine.VOXCAD, walkers, Env(), {"tiled": 2, "tiles_per_robot": k}, 300, 1000, tag="64 x 8^3 walkers", label="swimtiles")
+
+
+if __name__ == "__main__" and "shaperesults" in sys.argv[1:]:
+    # DESIGN section 8, large swimmers: host wall clock of the results loop of 64 full 14^3 swimmers (1178 mesh vertices each) after 200 steps.
+    #   shaperesults <device_shape> <device_shape_large>      one process per figure (scripts/ab_lib.py alternates two libraries)
+    opts = [int(a) for a in sys.argv[sys.argv.index("shaperesults") + 1:][:2]]
+    x, y, z = np.indices((14, 14, 14))
+    with open(os.path.join(G, "vxa", "lw_swim6.vxa")) as handle:
+        template = handle.read()
+    robots = [(3 + (x + y + z + i) % 2, {"<PhaseOffset>": np.round(0.37 * x - 0.23 * y + 0.11 * z + 0.01 * i, 3)}, None) for i in range(64)]
+    with engine.Engine(engine.VOXCAD_LAND_WATER, 0) as eng:
+        for key, value in zip(("device_shape", "device_shape_large"), opts):
+            if value:
+                eng.set_option(key, value)
+        eng.add_robots(template, robots)
+        eng.step(200)
+        t0 = time.perf_counter()
+        res = [eng.result(i) for i in range(eng.num_robots())]
+        dt = time.perf_counter() - t0
+    print("shaperesults lib %s options %s: results loop %.4f s, %d of %d robots on the host, hull end sum %.17g, robot volume end sum %.17g"
+          % (os.path.basename(engine.LIB_PATH), opts, dt, sum(r.reserved & 1 for r in res) if opts[0] else len(res), len(res),
+             sum(r.hull_volume_end for r in res), sum(r.robot_volume_end for r in res)), flush=True)

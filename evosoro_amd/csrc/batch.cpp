@@ -86,6 +86,43 @@ FusedVariant fused_variant(const RobotModel& M, int variant, const Options& opt)
     return fv;
 }
 
+// ---- the corner table of k_shape_curvature (batch.hpp) ----
+int curvature_corner_table(const RobotModel& M, std::vector<unsigned long long>& rec)
+{
+    const int n = M.nmv;
+    if (n <= 0 || n > VXH_SHAPE_LARGE_MAX_VERT) return 0;
+    const size_t nf = M.facet_vert.size() / 3;
+    for (int v : M.facet_vert) if (v < 0 || v >= n) return 0;   // (the kernel indexes its point planes with these)
+    // counting sort by `at`: stable, so a vertex's corners keep their facet order
+    std::vector<int> first(n + 1, 0);
+    auto corners = [&](auto&& emit) {
+        for (size_t f = 0; f < nf; ++f) {
+            const int a = M.facet_vert[3 * f], b = M.facet_vert[3 * f + 1], c = M.facet_vert[3 * f + 2];
+            emit(a, b, c);
+            if (b != a) emit(b, a, c);
+            if (c != a && c != b) emit(c, a, b);
+        }
+    };
+    corners([&](int at, int, int) { ++first[at + 1]; });
+    for (int i = 0; i < n; ++i) {
+        if (first[i + 1] == 0 || first[i + 1] > VXH_CURV_CHUNK) return 0;
+        first[i + 1] += first[i];
+    }
+    std::vector<int> fill(first.begin(), first.end() - 1), pq((size_t)2 * first[n]);
+    corners([&](int at, int p, int q) { const int k = fill[at]++; pq[(size_t)2 * k] = p; pq[(size_t)2 * k + 1] = q; });
+    const size_t begin = rec.size();
+    const unsigned long long idle = curv_record(0, 0, 0, 0, VXH_CURV_IDLE);
+    for (int i = 0; i < n; ++i) {
+        const int len = first[i + 1] - first[i];
+        const size_t used = (rec.size() - begin) % VXH_CURV_CHUNK;
+        if (used + len > VXH_CURV_CHUNK) rec.insert(rec.end(), VXH_CURV_CHUNK - used, idle);
+        for (int k = 0; k < len; ++k) rec.push_back(curv_record(i, pq[(size_t)2 * (first[i] + k)], pq[(size_t)2 * (first[i] + k) + 1], k == 0 ? len : 0, 0));
+    }
+    const size_t used = (rec.size() - begin) % VXH_CURV_CHUNK;
+    if (used) rec.insert(rec.end(), VXH_CURV_CHUNK - used, idle);
+    return (int)((rec.size() - begin) / VXH_CURV_CHUNK);
+}
+
 // ---- assemble_batch: the per-robot offsets into every shared table, then each robot's part of the tables ----
 namespace {
 
@@ -193,7 +230,19 @@ void lay_out_meshes(const std::vector<RobotModel>& robots, int variant, const Op
                 H.shape_large_lds = std::max(H.shape_large_lds, shape_large_lds_bytes(n));
             }
         }
-        if (!H.shape_list.empty() || !H.shape_large_list.empty()) H.shape_vert.assign((size_t)8 * total_mv, -1);
+        // device_curvature: the robots k_shape_curvature takes -- every one with a corner table, whatever the volume kernels do with it
+        if (opt.device_curvature) {
+            H.curv_rec_begin.assign(nr, 0); H.curv_pts_begin.assign(nr, 0); H.curv_n_chunk.assign(nr, 0);
+            for (int r = 0; r < nr; ++r) {
+                H.curv_rec_begin[r] = (long long)H.curv_rec.size();
+                H.curv_n_chunk[r] = curvature_corner_table(robots[r], H.curv_rec);
+                if (H.curv_n_chunk[r] == 0) continue;
+                const int n = robots[r].nmv;
+                if (n <= VXH_CURV_LDS_MAX_VERT) { H.curv_list.push_back(r); H.curv_max_nmv = std::max(H.curv_max_nmv, n); }
+                else { H.curv_hbm_list.push_back(r); H.curv_pts_begin[r] = H.curv_points; H.curv_points += (long long)3 * n; }
+            }
+        }
+        if (!H.shape_list.empty() || !H.shape_large_list.empty() || !H.curv_list.empty() || !H.curv_hbm_list.empty()) H.shape_vert.assign((size_t)8 * total_mv, -1);
     }
 }
 
@@ -410,7 +459,8 @@ void mesh_tables(const RobotModel& M, int r, HostBatch& H)
     if (M.nmv == 0) return;
     const size_t tm = (size_t)std::max(H.total_mv, 1);
     // (a robot of either shape kernel's list; both lists are in batch order)
-    const bool shape_listed = !H.shape_vert.empty() && (M.nmv <= VXH_SHAPE_MAX_VERT || std::binary_search(H.shape_large_list.begin(), H.shape_large_list.end(), r));
+    const bool shape_listed = !H.shape_vert.empty() && (M.nmv <= VXH_SHAPE_MAX_VERT || std::binary_search(H.shape_large_list.begin(), H.shape_large_list.end(), r) ||
+                                                        (!H.curv_n_chunk.empty() && H.curv_n_chunk[r] > 0));      // (... or of k_shape_curvature's)
     for (int i = 0; i < M.nmv; ++i) {
         unsigned w[3] = {0, 0, 0};
         for (int q = 0; q < 8; ++q) {

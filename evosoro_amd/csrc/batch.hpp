@@ -72,6 +72,14 @@ struct HostBatch {
     std::vector<long long> shape_large_off;
     long long shape_large_points = 0;
     size_t shape_large_lds = 0;
+    // option device_curvature (with device_shape): what k_shape_curvature reads beside shape_vert (DCurv, device_types.hpp).  Its lists are its own:
+    // every land_water robot that has a corner table, by nmv alone into the LDS instance's list or the HBM instance's.  Per robot the
+    // first record and the chunks of its table (0: not listed) and, for the HBM instance, the first double of its points.
+    std::vector<unsigned long long> curv_rec;
+    std::vector<long long> curv_rec_begin, curv_pts_begin;
+    std::vector<int> curv_n_chunk, curv_list, curv_hbm_list;
+    long long curv_points = 0;                 // doubles of the HBM instance's point table
+    int curv_max_nmv = 0;                      // most mesh vertices of a robot of curv_list (sizes the launch's LDS)
     // offsets of the per-robot pieces of the shared tables
     std::vector<int> vtab_off, btab_off;
     std::vector<long long> excl_off, col_off;
@@ -79,6 +87,12 @@ struct HostBatch {
     std::vector<int> img_idx;                  // slot of the robot's saved contact-row image (DBatch::rimg_*), colliding robots of up to 1024 voxels
     long long col_total = 0;
 };
+// The corner table of a robot's surface mesh for k_shape_curvature (device_types.hpp describes the records): walk the facets in order, emit
+// (at, p, q) for corner a, for b if b != a, for c if c != a && c != b (mesh_angle_excess: a vertex a facet lists twice counts once, in its
+// first role); group by `at`, facet order kept; lay the groups out in chunks of VXH_CURV_CHUNK records, padded so that none straddles a
+// chunk.  Appends to `rec` and returns the number of chunks; 0 (nothing appended): the robot has no table -- no mesh, more than
+// VXH_SHAPE_LARGE_MAX_VERT vertices, a vertex of no corner or of more than VXH_CURV_CHUNK.
+int curvature_corner_table(const RobotModel& M, std::vector<unsigned long long>& rec);
 // device_mem: the device's total memory in bytes (the contact-row budget is a third of it); 0 = unknown, rows are not cut
 HostBatch assemble_batch(const std::vector<RobotModel>& robots, int variant, const Options& opt, size_t device_mem);
 

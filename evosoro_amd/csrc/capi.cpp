@@ -262,8 +262,9 @@ int vxh_write_result_xml(const vxh_engine* ce, int robot, const char* path_or_nu
         if (m.vxa.variant == 1 && m.nmv > 0 && !m.vxa.curvatures_tmp_file.empty()) {
             curv_file = std::fopen(m.vxa.curvatures_tmp_file.c_str(), "wb");
             if (curv_file) {
-                std::vector<double> ex_start;
-                vxh::mesh_angle_excess(m, nullptr, nullptr, nullptr, ex_start);
+                // (both from the engine: mesh_angle_excess of the rest state and of the downloaded state, or -- option device_curvature -- the
+                // vectors k_shape_curvature left, with no download of the state)
+                const std::vector<double> ex_start = e->impl->angle_excess(robot, false);
                 ex_end = e->impl->angle_excess(robot, true);
                 shape_start = vxh::shape_complexity_as_the_reference_prints_it(m, ex_start);
                 shape_end = vxh::shape_complexity_as_the_reference_prints_it(m, ex_end);
@@ -318,8 +319,8 @@ int vxh_get_shape_descriptors(const vxh_engine* ce, int robot, int at_end, doubl
     if (bad_robot(e, robot)) return VXH_ERR_ARG;
     return guarded(e, [&] {
         vxh::MeshShape sh;
-        e->impl->shape(robot, at_end != 0, sh);
-        const bool none = sh.verts.empty();
+        e->impl->shape(robot, at_end != 0, sh, true);
+        const bool none = e->impl->robot(robot).nmv == 0;
         if (robot_volume) *robot_volume = none ? -1.0 : sh.robot_volume;
         if (hull_volume) *hull_volume = none ? -1.0 : sh.hull_volume;
         if (shape_complexity) *shape_complexity = none ? -1.0 : vxh::shape_complexity_as_the_reference_prints_it(e->impl->robot(robot), sh.angle_excess);

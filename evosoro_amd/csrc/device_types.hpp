@@ -216,6 +216,39 @@ struct DShape {
     double* large_pts;
 };
 
+// k_shape_curvature (kernels_curvature.hpp; engine option device_curvature): the angle excess of every mesh vertex of a land_water robot,
+// rest state and final state.  The kernel walks a CORNER TABLE the host lays out per robot (batch.cpp curvature_corner_table): one 8-byte
+// record per facet corner -- the vertex the angle lies at and the two others of the facet --, the corners of one vertex contiguous and in
+// facet order, the vertices ascending, in chunks of VXH_CURV_CHUNK records (one wavefront) that no vertex's group straddles:
+//   bits 0..15 `at` | 16..31 `p` | 32..47 `q` | 48..55 corners of `at` (in the first record of its group, 0 in the others) | 56..63 mark
+// mark VXH_CURV_IDLE: padding behind the last group of a chunk, no angle.  A robot with a vertex of no or of more than VXH_CURV_CHUNK
+// corners, or of more than VXH_SHAPE_LARGE_MAX_VERT vertices, has no table and stays on the host.
+// The points of a robot of up to VXH_CURV_LDS_MAX_VERT vertices lie in LDS, planes [3][np], 24 B per vertex: what the CU's 163840 B
+// hold once VXH_CURV_STATIC_LDS (the upper bound of the kernel's static variables; it has none of its own) is taken off.  Larger
+// robots get the instance whose points lie in the robot's range of a table in HBM.  Which instance: a function of nmv alone.
+enum { VXH_CURV_THREADS = 256, VXH_CURV_CHUNK = 64, VXH_CURV_IDLE = 1, VXH_CURV_STATIC_LDS = 1024,
+       VXH_CURV_LDS_MAX_VERT = (VXH_SHAPE_CU_LDS - VXH_CURV_STATIC_LDS) / 24 & ~1 };      // 6784
+VXH_HD inline size_t curv_lds_bytes(int nmv) { return (size_t)24 * ((nmv + 1) & ~1); }
+VXH_HD inline unsigned long long curv_record(int at, int p, int q, int group_len, int mark)
+{
+    return (unsigned long long)(unsigned)at | (unsigned long long)(unsigned)p << 16 | (unsigned long long)(unsigned)q << 32 |
+           (unsigned long long)(unsigned)group_len << 48 | (unsigned long long)(unsigned)mark << 56;
+}
+// what k_shape_curvature reads beside the batch and where it writes (uploaded when the option is on); the per-robot arrays are indexed
+// by the robot, so the kernel's two lists -- its own, independent of the volume kernels' -- only name robots
+struct DCurv {
+    const int* list;              // robots of the LDS instance, one workgroup each
+    const int* hbm_list;          // robots of the HBM-point instance
+    const int* vert;              // DShape::vert
+    const double* nom;            // DShape::nom
+    const unsigned long long* rec;      // the corner tables, robot after robot
+    const long long* rec_begin;   // [n_robots] first record of the robot's table
+    const int* n_chunk;           // [n_robots] its chunks of VXH_CURV_CHUNK records (0: not listed)
+    const long long* pts_begin;   // [n_robots] HBM instance: first double of the robot's [3][nmv] points in `pts`
+    double* pts;                  // written and read by that robot's workgroup alone
+    double* out;                  // [2][total_mv] angle excess of every mesh vertex: rest state, final state
+};
+
 // (collision partners per surface voxel: DRobot::col_cap; a row that would need more -> VXH_ROBOT_COL_OVERFLOW)
 
 // The words of DBatch::prof (developer builds, -DVXH_PHASE_TIMING): written by the kernels' timer macros and cross-checks (kernels_group.hpp,

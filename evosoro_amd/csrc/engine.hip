@@ -110,6 +110,12 @@ struct Engine::Device {
     int n_shape = 0, n_shape_large = 0;       // (the second: robots of k_shape_results_large, option device_shape_large)
     size_t shape_lds = 0, shape_large_lds = 0;
     std::vector<unsigned char> shape_listed;  // per robot
+    // engine option device_curvature: what k_shape_curvature reads and writes, the robots of its two instances, the LDS of the largest
+    DCurv curv{};
+    int n_curv = 0, n_curv_hbm = 0;
+    size_t curv_lds = 0;
+    std::vector<unsigned char> curv_listed;   // per robot
+    std::vector<int> mv_begin;                // per robot, its first mesh vertex in DCurv::out
     DRobotState* h_rstate = nullptr;          // pinned host mirror of DBatch::rstate: copied back on the call's own stream, behind its kernels
     size_t h_rstate_cap = 0;
     // a call that has been launched and not yet waited for (advance_launch / advance_finish)
@@ -210,6 +216,7 @@ struct Engine::Device {
         dbg_uploads.clear();
         results = nullptr;
         shape = DShape{}; n_shape = n_shape_large = 0;
+        curv = DCurv{}; n_curv = n_curv_hbm = 0; curv_listed.clear();
         B = DBatch{};
     }
     ~Device()                             // (the owner has made the device current)
@@ -402,6 +409,7 @@ const OptionDesc option_table[] = {
     {"dispatch_order",    &Options::dispatch_order,    OptionDesc::FLAG, OptionDesc::WHOLE, 0, 1,      false, false},
     {"device_shape",      &Options::device_shape,      OptionDesc::FLAG, OptionDesc::WHOLE, 0, 1,      true,  false},
     {"device_shape_large", &Options::device_shape_large, OptionDesc::FLAG, OptionDesc::WHOLE, 0, 1,    true,  false},
+    {"device_curvature",  &Options::device_curvature,  OptionDesc::FLAG, OptionDesc::WHOLE, 0, 1,      true,  false},
 };
 const OptionDesc& find_option(const std::string& key)
 {
@@ -605,8 +613,10 @@ void Engine::prepare()
 #endif
     D.n_shape = (int)H.shape_list.size();
     D.n_shape_large = (int)H.shape_large_list.size();
+    D.n_curv = (int)H.curv_list.size();
+    D.n_curv_hbm = (int)H.curv_hbm_list.size();
     D.shape_listed.assign(nr, 0);
-    if (D.n_shape > 0 || D.n_shape_large > 0) {
+    if (D.n_shape > 0 || D.n_shape_large > 0 || D.n_curv > 0 || D.n_curv_hbm > 0) {
         for (int r : H.shape_list) D.shape_listed[r] = 1;
         D.shape.list = D.upload(H.shape_list);
         D.shape.vert = D.upload(H.shape_vert);
@@ -622,6 +632,21 @@ void Engine::prepare()
         D.shape.large_off = D.upload(H.shape_large_off);
         D.shape.large_pts = D.alloc_raw<double>((size_t)H.shape_large_points);
         D.shape_large_lds = H.shape_large_lds;
+    }
+    D.curv_listed.assign(nr, 0);
+    if (D.n_curv > 0 || D.n_curv_hbm > 0) {      // device_curvature: the corner tables, the two lists, the output and -- only for a robot above the LDS cap -- the point table
+        for (int r = 0; r < nr; ++r) D.curv_listed[r] = H.curv_n_chunk[r] > 0;
+        D.curv.list = D.upload(H.curv_list);
+        D.curv.hbm_list = D.upload(H.curv_hbm_list);
+        D.curv.vert = D.shape.vert; D.curv.nom = D.shape.nom;
+        D.curv.rec = D.upload(H.curv_rec);
+        D.curv.rec_begin = D.upload(H.curv_rec_begin);
+        D.curv.n_chunk = D.upload(H.curv_n_chunk);
+        D.curv.pts_begin = D.upload(H.curv_pts_begin);
+        D.curv.pts = D.n_curv_hbm > 0 ? D.alloc_raw<double>((size_t)H.curv_points) : nullptr;
+        D.curv.out = D.alloc_zero<double>((size_t)2 * B.total_mv);
+        D.curv_lds = curv_lds_bytes(H.curv_max_nmv);
+        D.mv_begin = H.mv_begin;
     }
     B.small_angle_w = std::cos(VXH_SMALL_ANGLE_RAD * 0.5);                    // Vec3D.h:55-59
     B.smallish_angle_w = std::cos(VXH_HYST * VXH_SMALL_ANGLE_RAD * 0.5);
@@ -997,9 +1022,19 @@ int Engine::volume_trace(int robot, int which, double* out2n, int capacity)
     return n;
 }
 
+bool Engine::curvature_on_device(int robot) const
+{
+    return variant_ == 1 && opt_.device_shape && opt_.device_curvature && !opt_.host_results && prepared_ &&
+           robot < (int)dev_->curv_listed.size() && dev_->curv_listed[robot];
+}
+
 std::vector<double> Engine::angle_excess(int robot, bool at_end)
 {
     const RobotModel& M = robots_[robot];
+    if (curvature_on_device(robot)) {          // (the rest state too: the kernel forms both, and nothing but its vectors comes back)
+        if (!reduced_downloaded_) download_reduced();
+        return host_[robot].dev_curv[at_end ? 1 : 0];
+    }
     std::vector<double> out;
     if (!at_end) { mesh_angle_excess(M, nullptr, nullptr, nullptr, out); return out; }
     if (!prepared_) throw std::logic_error("angle excesses of the final state requested before vxh_run/vxh_step");
@@ -1010,15 +1045,29 @@ std::vector<double> Engine::angle_excess(int robot, bool at_end)
     return out;
 }
 
-void Engine::shape(int robot, bool at_end, MeshShape& out)
+void Engine::shape(int robot, bool at_end, MeshShape& out, bool descriptors_only)
 {
     const RobotModel& M = robots_[robot];
-    if (!at_end) { mesh_shape(M, nullptr, nullptr, nullptr, out); return; }
-    if (!prepared_) throw std::logic_error("the final mesh requested before vxh_run/vxh_step");
-    if (!state_downloaded_) download();
-    const HostState& H = host_[robot];
-    if (H.steps == 0 || (int)H.strain.size() != 6 * M.nvox) mesh_shape(M, nullptr, nullptr, nullptr, out);
-    else mesh_shape(M, H.pos.data(), H.quat.data(), H.strain.data(), out);
+    const bool dev_curv = descriptors_only && curvature_on_device(robot);
+    if (dev_curv) {                            // the three descriptors from the device; the two volumes only when k_shape_results did not decline the robot
+        if (!reduced_downloaded_) download_reduced();
+        const HostState& H = host_[robot];
+        if (!H.shape_fallback) {
+            out = MeshShape();
+            out.robot_volume = H.dev_robot_volume[at_end ? 1 : 0]; out.hull_volume = H.dev_hull_volume[at_end ? 1 : 0];
+            out.angle_excess = H.dev_curv[at_end ? 1 : 0];
+            return;
+        }
+    }
+    if (!at_end) mesh_shape(M, nullptr, nullptr, nullptr, out);
+    else {
+        if (!prepared_) throw std::logic_error("the final mesh requested before vxh_run/vxh_step");
+        if (!state_downloaded_) download();
+        const HostState& H = host_[robot];
+        if (H.steps == 0 || (int)H.strain.size() != 6 * M.nvox) mesh_shape(M, nullptr, nullptr, nullptr, out);
+        else mesh_shape(M, H.pos.data(), H.quat.data(), H.strain.data(), out);
+    }
+    if (dev_curv) out.angle_excess = host_[robot].dev_curv[at_end ? 1 : 0];
 }
 
 void Engine::bond_modes(long long* large_angle, long long* total)
@@ -1060,9 +1109,22 @@ void Engine::download_reduced()
             hs.resize(nr);
             HIP_OK(hipMemcpyAsync(hs.data(), D.shape.out, sizeof(DShapeResult) * nr, hipMemcpyDeviceToHost, D.stream));
         }
+        std::vector<double> hc;
+        if (D.n_curv > 0 || D.n_curv_hbm > 0) {          // ... and under device_curvature the angle excesses of both states, behind the volume kernels
+            if (D.n_curv > 0) launch_shape_curvature(D.B, D.curv, D.n_curv, D.curv_lds, D.stream);
+            if (D.n_curv_hbm > 0) launch_shape_curvature_hbm(D.B, D.curv, D.n_curv_hbm, D.stream);
+            HIP_OK(hipGetLastError());
+            hc.resize((size_t)2 * D.B.total_mv);
+            HIP_OK(hipMemcpyAsync(hc.data(), D.curv.out, sizeof(double) * hc.size(), hipMemcpyDeviceToHost, D.stream));
+        }
         HIP_OK(hipStreamSynchronize(D.stream));
         for (int r = 0; r < nr; ++r) {
             HostState& H = host_[r];
+            for (int k = 0; k < 2; ++k) {
+                if (hc.empty() || !D.curv_listed[r]) { H.dev_curv[k].clear(); continue; }
+                const double* from = hc.data() + (size_t)k * D.B.total_mv + D.mv_begin[r];
+                H.dev_curv[k].assign(from, from + robots_[r].nmv);
+            }
             H.shape_fallback = hs.empty() || !D.shape_listed[r] || hs[r].fallback != 0;
             if (!H.shape_fallback) for (int k = 0; k < 2; ++k) { H.dev_robot_volume[k] = hs[r].robot_volume[k]; H.dev_hull_volume[k] = hs[r].hull_volume[k]; }
             H.reduced = true;

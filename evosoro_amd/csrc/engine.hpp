@@ -27,6 +27,9 @@ struct HostState {                      // final/current state of one robot, dow
     // declined this robot (or was not launched for it) and the four tags come from the downloaded state
     double dev_robot_volume[2] = {0, 0}, dev_hull_volume[2] = {0, 0};
     bool shape_fallback = true;
+    // ... and option device_curvature: the angle excess of every mesh vertex [0] rest state, [1] final state from k_shape_curvature; empty: the
+    // robot is not on that kernel's list and mesh_angle_excess evaluates it from the downloaded state
+    std::vector<double> dev_curv[2];
     std::vector<double> cm_trace;                              // [4*k] (time, x, y, z): SS.CMTraceTime / SS.CMTrace
     // robots with <NormDistByVol>: SS.VolTrace, a volume per point of cm_trace, and the after-life [0] / frozen [1] traces,
     // [5*k] (time, x, y, z, volume): SS.CMTraceAfterLife + SS.VolTraceAfterLife, SS.CMTraceWhileFrozen + SS.VolTraceWhileFrozen
@@ -61,6 +64,8 @@ struct Options {
                                                // downloaded voxel state; a robot the kernel declines is evaluated on the host as before
     int device_shape_large = 0;                // ... and, with device_shape, robots of more than VXH_SHAPE_MAX_VERT (up to VXH_SHAPE_LARGE_MAX_VERT) mesh
                                                // vertices by k_shape_results_large (kernels_shape_large.hpp) instead of on the host
+    int device_curvature = 0;                  // ... and, with device_shape, the per-vertex angle excesses (<CurvaturesTmpFile>, <ShapeComplexityStart/End>) of robots
+                                               // of up to VXH_SHAPE_LARGE_MAX_VERT vertices by k_shape_curvature (kernels_curvature.hpp) instead of on the host
 };
 
 class Engine {
@@ -89,7 +94,9 @@ public:
     int volume_trace(int robot, int which, double* out2n, int capacity);
     const HostState& traces_of(int robot);                     // cm_trace, vol_trace, xtrace of the robot (downloads them if needed)
     std::vector<double> angle_excess(int robot, bool at_end);  // land_water: discrete curvature of every mesh vertex, rest state / current state
-    void shape(int robot, bool at_end, struct MeshShape& out); // the surface mesh and its descriptors, rest state / current state
+    // the surface mesh and its descriptors, rest state / current state; descriptors_only: the caller reads no vertices and no facets (under
+    // the option device_curvature they are then not formed, and the state is not downloaded, when the device has all three descriptors)
+    void shape(int robot, bool at_end, struct MeshShape& out, bool descriptors_only = false);
     void bond_modes(long long* large_angle, long long* total);   // SmallAngle flags of every bond, downloaded
     void set_option(const std::string& key, double value);
     void check_option(const std::string& key, double value) const;   // throws what set_option would throw, changes nothing
@@ -118,6 +125,7 @@ private:
     void download();
     void download_control(bool already_copied = false);
     void download_reduced();                   // k_results + the traces: what results need, without the voxel state
+    bool curvature_on_device(int robot) const; // option device_curvature is in force and k_shape_curvature evaluates this robot of the prepared batch
     int variant_, device_id_;
     std::vector<RobotModel> robots_;
     std::vector<HostState> host_;
@@ -160,7 +168,7 @@ public:
     int volume_trace(int robot, int which, double* out2n, int capacity);
     const HostState& traces_of(int robot);
     std::vector<double> angle_excess(int robot, bool at_end);
-    void shape(int robot, bool at_end, struct MeshShape& out);
+    void shape(int robot, bool at_end, struct MeshShape& out, bool descriptors_only = false);
     void bond_modes(long long* large_angle, long long* total);
     int n_devices() const { return (int)engines_.size(); }
 

@@ -229,10 +229,10 @@ std::vector<double> EngineSet::angle_excess(int robot, bool at_end)
     flush_pending(); distribute();
     return engines_[where_[robot].first]->angle_excess(where_[robot].second, at_end);
 }
-void EngineSet::shape(int robot, bool at_end, MeshShape& out)
+void EngineSet::shape(int robot, bool at_end, MeshShape& out, bool descriptors_only)
 {
     flush_pending(); distribute();
-    engines_[where_[robot].first]->shape(where_[robot].second, at_end, out);
+    engines_[where_[robot].first]->shape(where_[robot].second, at_end, out, descriptors_only);
 }
 void EngineSet::bond_modes(long long* large_angle, long long* total)
 {

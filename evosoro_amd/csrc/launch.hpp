@@ -1,5 +1,5 @@
 // Host-side launch entry points of every kernel.  Each kernel family is its own translation unit (launch_fused_*.hip,
-// launch_wide.hip, launch_tiled.hip, launch_stream.hip, launch_shape.hip) so that the Makefile compiles them side by side and a change to one family
+// launch_wide.hip, launch_tiled.hip, launch_stream.hip, launch_shape.hip, launch_curvature.hip) so that the Makefile compiles them side by side and a change to one family
 // recompiles that family only; engine.hip (device memory, the call loop, graph capture) compiles no kernel and sees these declarations.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -54,6 +54,10 @@ void launch_results(const DBatch& B, int n_robots, DResult* out, hipStream_t s);
 void launch_shape_results(const DBatch& B, const DShape& Q, int count, size_t lds, hipStream_t s);
 // k_shape_results_large (kernels_shape_large.hpp): one workgroup per robot of Q.large_list; lds: the most shape_large_lds_bytes of them
 void launch_shape_results_large(const DBatch& B, const DShape& Q, int count, size_t lds, hipStream_t s);
+// k_shape_curvature<false> (kernels_curvature.hpp): one workgroup per robot of C.list; lds: curv_lds_bytes of the largest.  <true>: the robots
+// of C.hbm_list, points in C.pts
+void launch_shape_curvature(const DBatch& B, const DCurv& C, int count, size_t lds, hipStream_t s);
+void launch_shape_curvature_hbm(const DBatch& B, const DCurv& C, int count, hipStream_t s);
 // k_dispatch_order (kernels_order.hpp): perm = the `count` list entries by descending expected cost of a launch of `len` steps (0: the list order)
 void launch_dispatch_order(const DispatchCost* cost, int count, int len, int* perm, hipStream_t s);
 

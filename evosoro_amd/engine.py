@@ -5,7 +5,9 @@ the product path never routes through a CPU implementation.
 
 Engine options (Engine.set_option, documented in include/vxhip.h) pass through by name; among them "device_shape": 1 = the volume and
 convex-hull tags of land_water robots come from the device and result() no longer downloads the voxel state (default 0), and with it
-"device_shape_large": 1 = also those of robots of more than 1024 (up to 8192) mesh vertices, which otherwise stay on the host (default 0).
+"device_shape_large": 1 = also those of robots of more than 1024 (up to 8192) mesh vertices, which otherwise stay on the host (default 0);
+"device_curvature": 1 = with "device_shape", angle_excess(), the <CurvaturesTmpFile> / <ShapeComplexity*> of write_result_xml() and the
+complexity of shape_descriptors() come from the device too, and the file route no longer downloads the voxel state (default 0).
 """
 import ctypes
 import os

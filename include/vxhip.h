@@ -269,7 +269,15 @@ int  vxh_count_bond_modes(const vxh_engine* e, long long* large_angle_out, long 
  *                       (k_shape_results_large: points in device memory, the hull in LDS; same agreement with the host).  Its face
  *                       list holds about 3000 faces: a robot whose hull has more vertices than about 1500 is declined like a
  *                       degenerate one (host, bit 0 of reserved).  No effect without "device_shape"; robots of up to 1024 vertices are
- *                       evaluated exactly as without it.  Set it before the first vxh_run / vxh_step.  Default 0. */
+ *                       evaluated exactly as without it.  Set it before the first vxh_run / vxh_step.  Default 0.
+ *   "device_curvature"  1 = with "device_shape", the per-vertex angle excesses of land_water robots of up to 8192 mesh vertices -- what
+ *                       vxh_get_angle_excess returns, vxh_write_result_xml writes to <CurvaturesTmpFile> and prints as
+ *                       <ShapeComplexityStart/End>, and the complexity of vxh_get_shape_descriptors -- are formed on the device, rest state
+ *                       and final state (k_shape_curvature: the host's vertices and the host's order of summation; a value differs from
+ *                       the host's only by what the device's acos differs from the host's, a few units of the last place).  The file
+ *                       route then never downloads the voxel state.  Independent of which volume kernel takes the robot and of bit 0
+ *                       of reserved; vxh_get_mesh stays on the host.  No effect without "device_shape".  Set it before the first
+ *                       vxh_run / vxh_step.  Default 0. */
 int  vxh_set_option(vxh_engine* e, const char* key, double value);
 
 const char* vxh_strerror(int status);

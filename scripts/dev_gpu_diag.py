@@ -1503,3 +1503,36 @@ if __name__ == "__main__" and "shaperesults" in sys.argv[1:]:
     print("shaperesults lib %s options %s: results loop %.4f s, %d of %d robots on the host, hull end sum %.17g, robot volume end sum %.17g"
           % (os.path.basename(engine.LIB_PATH), opts, dt, sum(r.reserved & 1 for r in res) if opts[0] else len(res), len(res),
              sum(r.hull_volume_end for r in res), sum(r.robot_volume_end for r in res)), flush=True)
+
+
+if __name__ == "__main__" and "curvresults" in sys.argv[1:]:
+    # DESIGN section 8, the file route: 512 random 8^3 swimmers on lw_swim6's settings, a <CurvaturesTmpFile> in a temporary directory, run to
+    # completion; then the host wall clock of ONE of the two loops over the robots (a fresh process per figure; scripts/ab_lib.py alternates two
+    # libraries):
+    #   curvresults <device_shape + device_shape_large + device_curvature: 0 | 1> <loop: excess | xml>
+    import re
+    args = sys.argv[sys.argv.index("curvresults") + 1:]
+    on, loop = int(args[0]), args[1]
+    tmp = tempfile.mkdtemp()
+    with open(os.path.join(G, "vxa", "lw_swim6.vxa")) as handle:
+        template = re.sub(r"<CurvaturesTmpFile>.*?</CurvaturesTmpFile>", "<CurvaturesTmpFile>%s</CurvaturesTmpFile>" % os.path.join(tmp, "curvatures.txt"), handle.read())
+    x, y, z = np.indices((8, 8, 8))
+    robots = [(workloads.random_material((8, 8, 8), i), {"<PhaseOffset>": np.round(0.37 * x - 0.23 * y + 0.11 * z + 0.01 * i, 3)}, None) for i in range(512)]
+    with engine.Engine(engine.VOXCAD_LAND_WATER, 0) as eng:
+        if on:
+            for key in ("device_shape", "device_shape_large", "device_curvature"):
+                eng.set_option(key, 1)
+        eng.add_robots(template, robots)
+        eng.run()
+        n = eng.num_robots()
+        t0 = time.perf_counter()
+        if loop == "excess":
+            check = sum(float(np.nansum(eng.angle_excess(i, True))) for i in range(n))
+        else:
+            for i in range(n):
+                eng.write_result_xml(i, os.path.join(tmp, "out_%d.xml" % i))
+            check = float(sum(os.path.getsize(os.path.join(tmp, "out_%d.xml" % i)) for i in range(n)))
+        dt = time.perf_counter() - t0
+        host = sum(eng.result(i).reserved & 1 for i in range(n)) if on else n
+    print("curvresults lib %s option %d loop %s: %.4f s for %d robots, %d of them with the volume tags from the host, check sum %.17g"
+          % (os.path.basename(engine.LIB_PATH), on, loop, dt, n, host, check), flush=True)

@@ -1,12 +1,12 @@
 #!/bin/bash
 # registers / scratch / occupancy of every kernel of the engine, as the compiler reports them (no GPU needed)
-# usage: scripts/kernel_resources.sh [-f family] [extra hipcc flags]     family: launch_fused_land | launch_fused_mesh | launch_wide | launch_tiled | launch_stream | launch_shape (default: all)
+# usage: scripts/kernel_resources.sh [-f family] [extra hipcc flags]     family: launch_fused_land | launch_fused_mesh | launch_wide | launch_tiled | launch_stream | launch_shape | launch_curvature (default: all)
 cd "$(dirname "$0")/../evosoro_amd/csrc"
-FAMS="launch_fused_land launch_fused_mesh launch_wide launch_tiled launch_stream launch_shape"
+FAMS="launch_fused_land launch_fused_mesh launch_wide launch_tiled launch_stream launch_shape launch_curvature"
 if [ "$1" = "-f" ]; then FAMS="$2"; shift 2; fi
 for f in $FAMS; do
-  UNIT=""      # (the shape kernels' unit is built without contraction and packed FP32, as the Makefile builds it)
-  if [ "$f" = "launch_shape" ]; then UNIT="-ffp-contract=off -Xclang -target-feature -Xclang -packed-fp32-ops"; fi
+  UNIT=""      # (the shape and curvature kernels' units are built without contraction and packed FP32, as the Makefile builds them)
+  if [ "$f" = "launch_shape" ] || [ "$f" = "launch_curvature" ]; then UNIT="-ffp-contract=off -Xclang -target-feature -Xclang -packed-fp32-ops"; fi
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -mllvm -disable-machine-licm $UNIT "$@" --cuda-device-only -Rpass-analysis=kernel-resource-usage -c $f.hip -o /tmp/vxh_${f}_res.o 2>&1 &
 done 2>&1 | cat |
 python3 -c '

@@ -33,6 +33,10 @@ FusedVariant fused_variant(const RobotModel& M, int variant, const Options& opt)
     FusedVariant fv;
     const size_t lds_max = 160 * 1024 - VXH_FUSED_STATIC_LDS;
     const int n = M.nvox;
+    // a robot under StopConditionType 4-7 takes the STATS instance of the kernel it would take anyway; the pass's per-wavefront words are
+    // part of its LDS need (the last VXH_STAT_LDS doubles of the launch's dynamic LDS)
+    fv.stats = stat_rules(M) ? 1 : 0;
+    const size_t stat_lds = fv.stats ? (size_t)8 * VXH_STAT_LDS : 0;
     if (n == 0 || n > 1024 || M.bond_classes.size() > 4095) return fv;   // (12 class bits in a bond entry; a robot of 1024 voxels has at most 3072 bonds)
     if (wide_listed(M, variant, opt)) {
         // the wide kernel when its LDS layout fits (mirrors the top of k_robot_wide): pose tile, record region, class tables,
@@ -40,7 +44,7 @@ FusedVariant fused_variant(const RobotModel& M, int variant, const Options& opt)
         const WideLayout W = wide_layout(M, variant);
         const int mesh = M.nmv > 0 ? 1 : 0;
         auto wneed = [&](bool tables_in_lds) {
-            return (size_t)(8 * WIDE_BLOCK + W.region) * 8 +
+            return (size_t)(8 * WIDE_BLOCK + W.region) * 8 + stat_lds +
                    (tables_in_lds ? M.bond_classes.size() * sizeof(DBondClass) + M.vox_classes.size() * sizeof(DVoxClass) : 0) +
                    (mesh ? (size_t)48 * WIDE_BLOCK : 0) + (M.vxa.self_col_enabled ? (size_t)8 * WIDE_BLOCK : 0);
         };
@@ -66,7 +70,7 @@ FusedVariant fused_variant(const RobotModel& M, int variant, const Options& opt)
     // (mirrors the layout at the top of k_robot_steps; SLIM = the 768-thread MESH variant, phases and strains in HBM)
     const bool slim = fluid && block == 768;
     auto need = [&](int nacc, bool tables_in_lds) {
-        return (size_t)(8 + 6 * nacc + (slim ? 0 : 2)) * block * 8 +
+        return (size_t)(8 + 6 * nacc + (slim ? 0 : 2)) * block * 8 + stat_lds +
                (tables_in_lds ? M.bond_classes.size() * sizeof(DBondClass) + M.vox_classes.size() * sizeof(DVoxClass) : 0) +
                (in_fluid ? (size_t)24 * M.nmv : 0) + ((fluid && nacc == 2 && !slim) ? (size_t)48 * block : 0);
     };
@@ -289,6 +293,14 @@ void lay_out_tables(const std::vector<RobotModel>& robots, int variant, const Op
     H.col_total = H.col_off[nr];
     H.vtab.resize(H.vtab_off[nr]);
     H.btab.resize(H.btab_off[nr]);
+    // robots under StopConditionType 4-7: their slots of the history rings, the strain-energy factors of every bond class of the batch
+    H.n_stat = 0;
+    for (int r = 0; r < nr; ++r) if (robots[r].nvox > 0 && stat_rules(robots[r])) ++H.n_stat;
+    if (H.n_stat > 0) {
+        H.stat_slot.assign(nr, -1);
+        for (int r = 0, k = 0; r < nr; ++r) if (robots[r].nvox > 0 && stat_rules(robots[r])) H.stat_slot[r] = k++;
+        H.bond_energy.assign((size_t)3 * std::max(H.btab_off[nr], 1), 0.0);
+    }
     H.excl.assign((size_t)H.excl_off[nr], 0ull);
 }
 
@@ -318,6 +330,10 @@ void class_tables(const RobotModel& M, int r, HostBatch& H)
         d.dT2 = c.sq_a2i2 * zh; d.dG2 = c.sq_b2fm2 * zh; d.dH2 = c.sq_b3i2 * zh;
         d.homogeneous = c.homogeneous;
         H.btab[btab_begin + i] = d;
+        if (!H.bond_energy.empty()) {      // CVX_Bond::UpdateConstants, VX_Bond.cpp:144-147: _2xA1Inv, _2xA2Inv, _3xB3yInv (== _3xB3zInv)
+            double* e = &H.bond_energy[(size_t)3 * (btab_begin + i)];
+            e[0] = 1.0 / (c.a1 * 2.0); e[1] = 1.0 / (c.a2 * 2.0); e[2] = 1.0 / (c.b3 * 3.0);
+        }
     }
     DRobot& R = H.robot[r];
     R.vtab_begin = vtab_begin; R.n_vclass = (int)M.vox_classes.size(); R.btab_begin = btab_begin; R.n_bclass = (int)M.bond_classes.size();
@@ -577,6 +593,7 @@ std::vector<int> tile_candidates(const std::vector<RobotModel>& robots, int vari
         // round 5, in a FLUID: the tile then carries its part of the drag mesh, and the voxels a mesh vertex averages over -- up to
         // seven, across tile boundaries, diagonal neighbours included -- come through the exchange buffer with their strains
         if (M.nvox == 0) continue;
+        if (stat_rules(M)) continue;         // StopConditionType 4-7: no tiles (a cross-workgroup sum on every step); the streaming kernels take what is left
         const int block = fused_variant(M, variant, opt).block;
         if (tiled_now == 2 || !opt.fused || block == 0 || (small_population && block >= 768)) cand.push_back(r);
     }
@@ -792,10 +809,12 @@ void form_groups(const std::vector<RobotModel>& robots, int variant, const Optio
     for (int r = 0; r < nr; ++r) {
         if (P.robot_tiled[r]) continue;
         const FusedVariant fv = fused_variant(robots[r], variant, opt);
+        // (a robot under StopConditionType 4-7 that neither kernel takes -- more than 1024 voxels, oversized tables -- is never tiled
+        // (tile_candidates): it falls through here to the streaming kernels, whose statistics pass is k_stream_stats)
         if (fv.block == 0) continue;                              // streaming kernels
         GroupPlan* g = nullptr;
-        for (auto& q : P.groups) if (q.block == fv.block && q.nacc == fv.nacc && q.fluid == fv.fluid && q.tabg == fv.tabg && q.wide == fv.wide && q.two_tiles == fv.two_tiles) g = &q;
-        if (!g) { P.groups.emplace_back(); g = &P.groups.back(); g->block = fv.block; g->nacc = fv.nacc; g->fluid = fv.fluid; g->tabg = fv.tabg; g->wide = fv.wide; g->two_tiles = fv.two_tiles; }
+        for (auto& q : P.groups) if (q.block == fv.block && q.nacc == fv.nacc && q.fluid == fv.fluid && q.tabg == fv.tabg && q.wide == fv.wide && q.two_tiles == fv.two_tiles && q.stats == fv.stats) g = &q;
+        if (!g) { P.groups.emplace_back(); g = &P.groups.back(); g->block = fv.block; g->nacc = fv.nacc; g->fluid = fv.fluid; g->tabg = fv.tabg; g->wide = fv.wide; g->two_tiles = fv.two_tiles; g->stats = fv.stats; }
         g->robots.push_back(r);
         g->lds = std::max(g->lds, fv.lds);
     }

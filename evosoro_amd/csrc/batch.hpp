@@ -22,7 +22,11 @@ bool wide_listed(const RobotModel& M, int variant, const Options& opt);
 int resident_block(int n);
 // Resident kernel (kernels_fused.hpp) or wide kernel, one workgroup per robot: the variant follows from the robot's size, fluid, and the
 // LDS need of its own tables.  block == 0: neither takes the robot.
-struct FusedVariant { int block = 0, nacc = 0, fluid = 0, tabg = 0, wide = 0, two_tiles = 0; size_t lds = 0; };
+// stats: the robot is under StopConditionType 4-7 and takes the STATS instance of its kernel (stat_rules below) -- the same kernel choice as
+// under any other rule, with VXH_STAT_LDS doubles more of dynamic LDS (the contact rows give them up where the layout is full).
+struct FusedVariant { int block = 0, nacc = 0, fluid = 0, tabg = 0, wide = 0, two_tiles = 0, stats = 0; size_t lds = 0; };
+// the energy and motion stop rules (CVX_Sim::StopConditionMet, VX_Sim.cpp:1427-1460), which need whole-robot statistics after every step
+inline bool stat_rules(const RobotModel& M) { return M.vxa.stop_type >= 4 && M.vxa.stop_type <= 7; }
 FusedVariant fused_variant(const RobotModel& M, int variant, const Options& opt);
 
 // Every host table of a batch, in the layout the kernels read (DBatch, device_types.hpp, describes each), and the scalars that go with them.
@@ -86,6 +90,11 @@ struct HostBatch {
     std::vector<int> col_cap;
     std::vector<int> img_idx;                  // slot of the robot's saved contact-row image (DBatch::rimg_*), colliding robots of up to 1024 voxels
     long long col_total = 0;
+    // robots under StopConditionType 4-7: per robot its number among them or -1 (DStat::stat_slot; the history rings are sized by n_stat),
+    // and per row of btab the three strain-energy factors (DStat::bond_energy).  Both empty when the batch holds no such robot.
+    std::vector<int> stat_slot;
+    std::vector<double> bond_energy;
+    int n_stat = 0;
 };
 // The corner table of a robot's surface mesh for k_shape_curvature (device_types.hpp describes the records): walk the facets in order, emit
 // (at, p, q) for corner a, for b if b != a, for c if c != a && c != b (mesh_angle_excess: a vertex a facet lists twice counts once, in its
@@ -101,6 +110,7 @@ struct GroupPlan {
     int block = 0, nacc = 0, fluid = 0, tabg = 0;   // template arguments of k_robot_steps
     int wide = 0;                     // 1: k_robot_wide<block, fluid, tabg> (kernels_wide.hpp)
     int two_tiles = 0;                // wide kernel: a second pose tile in LDS (two barriers per step instead of three)
+    int stats = 0;                    // the STATS instances: robots under StopConditionType 4-7 (never measured for the dispatch order)
     int count = 0;
     bool order_use = false;           // short launches are dispatched "robots due for a broad-phase run first" (kernels_fused.hpp fused_dispatch_slot),
                                       // long ones by measured cost, longest first (dispatch_order.hpp): k_robot_steps groups with colliding robots

@@ -283,7 +283,7 @@ enum ProfSlot {
 // all device pointers of a batch; passed to kernels by value
 struct DBatch {
     int n_robots, nv;                 // nv = total padded voxel slots (multiple of 64 per robot)
-    int dbg, pad1;                    // developer switches (scripts/dev_gpu_diag.py), 0 in production
+    int dbg, stat_lo;                 // developer switches (scripts/dev_gpu_diag.py), 0 in production; stat_lo / stat_hi: the address of the batch's DStat (below)
     const DRobot* robot;
     DRobotState* rstate;
     DRobotState* rstate_mirror;       // the same blocks in pinned host memory (or null): the resident kernels write a robot's block to both when a launch ends
@@ -334,7 +334,7 @@ struct DBatch {
     // segments, every thread's row descriptor), saved whenever it is built and streamed back at the start of the next launch -- one
     // round trip of coalesced loads instead of ordinal -> count -> scan -> rows, three dependent round trips and three barriers
     int* rimg_code; double* rimg_a1; int* rimg_seg; int* rimg_rowd;     // [n_img * VXH_RIMG_CAP] x 2, [n_img * 64], [nv]
-    int col_rows, pad2;               // total surface voxels of colliding robots
+    int col_rows, stat_hi;            // total surface voxels of colliding robots
     int* col_partner;                 // per robot a block [col_cap][nsurf] (partner-major; kernels_physics.hpp col_at) of global voxel slots
     double* col_a1;                   // same shape: linear stiffness a1 of that collision bond
     // land_water fluid drag (LW/VX_Sim.cpp:1516-1597): deformable surface mesh of every fluid robot
@@ -396,5 +396,31 @@ struct DBatch {
     // constants from Vec3D.h evaluated by the host libm (thresholds of the small-angle logic)
     double small_angle_w, smallish_angle_w, slthresh_acos2sqrt;
 };
+
+// What the STATS kernel instances (robots under StopConditionType 4-7) read beside the batch: per robot its number among such robots or -1;
+// their history rings, [slot][VXH_STAT_PLANES][VXH_STAT_HISTORY] doubles (stat_entry below); per bond class of the batch (the rows of
+// bclass_tab) the three factors of CVXS_Bond::CalcStrainEnergy: 1 / (2 a1), 1 / (2 a2), 1 / (3 b3).  The record lies in device memory and
+// DBatch carries its address in two words that used to be padding (stat_lo / stat_hi; both 0: no such robot in the batch): a DBatch that
+// grows by a pointer changes the register allocation of every kernel that takes it, and the kernels of all other robots are to stay what
+// they were, instruction for instruction.
+// The streaming kernels pass their share through HBM: bond_e, [3 * nv] the strain energy of every bond slot as k_bonds_stats left it; sums,
+// [slot][3] TotalObjKineticE, TotalObjStrainE, MaxVoxVel^2 of the step as k_stream_stats reduced them (kernels_stream.hpp).
+struct DStat { const int* stat_slot; double* stat_ring; const double* bond_energy; double* bond_e; double* sums; };
+// the one place that packs and unpacks the address (the two words sit far apart in DBatch); the size is pinned so that a change of DBatch
+// is a decision, not an accident: every kernel takes it by value
+static_assert(sizeof(DBatch) == 640, "DBatch changed size: every kernel's argument block and register allocation changes with it");
+inline void stat_address_set(DBatch& B, const DStat* at) { const unsigned long long a = (unsigned long long)at; B.stat_lo = (int)(unsigned)a; B.stat_hi = (int)(unsigned)(a >> 32); }
+VXH_HD inline const DStat* stat_address(const DBatch& B) { return (const DStat*)(((unsigned long long)(unsigned)B.stat_hi << 32) | (unsigned)B.stat_lo); }
+
+// The histories of CVX_Sim::UpdateStats (VX_Sim.cpp:1685-1687: MaxMoveHistory, KinEHistory, TotEHistory; HISTORY_SIZE entries, the newest at
+// index 0) as rings keyed by the step count: the entry of the step that raised CurStepCount to s lies at s % VXH_STAT_HISTORY, so history
+// index i after step s is the entry of step s - i -- and the reference's initial -1 exactly when s - i < 1: no step has written it yet.  A
+// ring therefore needs no initialisation, and vxh_reset (steps = 0) empties it.  StopConditionMet samples every VXH_STAT_JUMP-th index.
+enum { VXH_STAT_HISTORY = 10000, VXH_STAT_JUMP = 1000, VXH_STAT_SAMPLES = 9, VXH_STAT_PLANES = 3,
+       VXH_STAT_MOVE = 0, VXH_STAT_KINE = 1, VXH_STAT_TOTE = 2,
+       VXH_STAT_LDS = 64 };          // doubles at the end of the dynamic LDS of a STATS instance: per wavefront the two sums and the maximum
+VXH_HD inline size_t stat_entry(int slot, int plane, int step) { return ((size_t)slot * VXH_STAT_PLANES + plane) * VXH_STAT_HISTORY + (size_t)(step % VXH_STAT_HISTORY); }
+VXH_HD inline int stat_plane_of(int stop_type) { return stop_type == 4 ? VXH_STAT_TOTE : (stop_type == 5 ? VXH_STAT_KINE : VXH_STAT_MOVE); }
+
 
 }  // namespace vxh

@@ -88,6 +88,9 @@ struct Engine::Device {
     std::vector<int> surf_begin;
     int total_surf = 0;
     long long max_planned = 0;
+    bool any_stat = false;                          // the batch holds robots under StopConditionType 4-7
+    bool stat_rest = false, stat_all = false;       // ... and the streaming kernels step one of them (masks streamed_rest / streamed_all)
+    std::vector<DStat> stat_host;                   // ... and the record their kernels read (DBatch::stat_lo / stat_hi)
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
     int graph_rounds = 0;
@@ -561,6 +564,21 @@ void Engine::prepare()
     }
     B.col_partner = D.alloc_raw<int>((size_t)std::max<long long>(H.col_total, 1));     // (entries beyond col_cnt are never read)
     B.col_a1 = D.alloc_raw<double>((size_t)std::max<long long>(H.col_total, 1));
+    // robots under StopConditionType 4-7: three history rings of VXH_STAT_HISTORY doubles each (240 KB per robot; keyed by the step count, so
+    // they need no initial value and a reset -- this function again -- empties them) and the strain-energy factors of the bond classes;
+    // nothing is allocated for a batch without such a robot
+    B.stat_lo = B.stat_hi = 0;
+    if (H.n_stat > 0) {
+        std::vector<DStat>& q = D.stat_host;      // (a member: the copy may still be in flight when this block ends)
+        q.assign(1, DStat{nullptr, nullptr, nullptr, nullptr, nullptr});
+        q[0].stat_slot = D.upload(H.stat_slot);
+        q[0].bond_energy = D.upload(H.bond_energy);
+        q[0].stat_ring = D.alloc_raw<double>((size_t)H.n_stat * VXH_STAT_PLANES * VXH_STAT_HISTORY);
+        q[0].bond_e = D.alloc_zero<double>((size_t)3 * nv);      // (the streaming kernels' share of the pass; never read where no bond wrote)
+        q[0].sums = D.alloc_zero<double>((size_t)3 * H.n_stat);
+        stat_address_set(B, D.upload(q));      // (DBatch keeps its size: device_types.hpp DStat)
+    }
+    D.any_stat = H.n_stat > 0;
     hs.mark("allocations + uploads");
     LaunchPlan P = plan_launches(robots_, H, variant_, opt_, tiling_allowed_, D.n_cu);
     D.tile_launches.clear();
@@ -590,6 +608,9 @@ void Engine::prepare()
     B.tile_mvox = D.upload(P.tile_mvox);
     B.tile_mv = D.alloc_zero<unsigned long long>(std::max<size_t>(1, P.tiles.size()) * 3 * VXH_TILE_MV_STRIDE);
     D.n_rest = P.n_rest; D.n_all = P.n_all;
+    D.stat_rest = D.stat_all = false;
+    for (size_t r = 0; r < robots_.size(); ++r)
+        if (robots_[r].nvox > 0 && stat_rules(robots_[r])) { D.stat_rest = D.stat_rest || P.streamed_rest[r]; D.stat_all = D.stat_all || P.streamed_all[r]; }
     D.streamed_all = D.upload(P.streamed_all);
     D.streamed_rest = D.upload(P.streamed_rest);
     D.groups.clear();
@@ -671,12 +692,12 @@ void Engine::prepare()
 void Engine::reset() { if (!robots_.empty()) prepare(); }
 
 // (which kernel variant takes a robot -- fused_variant, wide_listed, resident_block -- is decided in batch.cpp; a Group carries the answer)
-static void launch_group(const DBatch& B, int block, bool fluid, bool tabg, bool wide, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters, int two_tiles = 0,
+static void launch_group(const DBatch& B, int block, bool fluid, bool tabg, bool wide, bool stats, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters, int two_tiles = 0,
                          const unsigned long long* order_in = nullptr, unsigned long long* order_out = nullptr, bool cost = false)
 {
-    if (wide) { launch_wide_group(B, fluid, tabg, list, count, lds, s, cap, iters, two_tiles); return; }
+    if (wide) { launch_wide_group(B, fluid, tabg, stats, list, count, lds, s, cap, iters, two_tiles); return; }
     if (fluid) launch_fused_mesh(B, block, tabg, list, count, lds, s, cap, iters, order_in, order_out, cost);
-    else launch_fused_land(B, block, tabg, list, count, lds, s, cap, iters, order_in, order_out, cost);
+    else launch_fused_land(B, block, tabg, list, count, lds, s, cap, iters, order_in, order_out, cost, stats);
 }
 
 // A call in two halves: advance_launch enqueues every kernel of the call and returns; advance_finish waits for the device, reads
@@ -769,7 +790,8 @@ void Engine::advance_launch(long long max_rounds)
                 // kernel instances that measure (COST), with k_dispatch_order in front (length 0: all keys equal, the list order).
                 const long long len = std::min<long long>(iters, std::max<long long>(1, todo - done));
                 const bool is_short = len <= VXH_ORDER_MAX_STEPS;
-                const bool measure = g.order_use && !is_short && (opt_.dispatch_order != 0 || prof_order);
+                // (a STATS group is never measured -- there are no COST + STATS instances --: its long launches keep the list order, its short ones the flag rule)
+                const bool measure = g.order_use && !g.stats && !is_short && (opt_.dispatch_order != 0 || prof_order);
                 const bool dyn = g.order_use && g.order_valid && is_short && opt_.dispatch_order != 0;
                 hipStream_t st = single ? D.stream : g.stream;
                 const unsigned long long* order_in = dyn ? g.order_bits[g.order_cur] : nullptr;
@@ -779,7 +801,7 @@ void Engine::advance_launch(long long max_rounds)
                     order_in = (const unsigned long long*)g.order_perm;
                     g.cost_valid = true; g.last_ordered = by_cost; g.last_len = len;
                 }
-                launch_group(B, g.block, g.fluid != 0, g.tabg != 0, g.wide != 0, g.list, g.count, g.lds, st, cap, iters, g.two_tiles, order_in,
+                launch_group(B, g.block, g.fluid != 0, g.tabg != 0, g.wide != 0, g.stats != 0, g.list, g.count, g.lds, st, cap, iters, g.two_tiles, order_in,
                              g.order_use ? g.order_bits[g.order_cur ^ 1] : nullptr, measure);
                 if (g.order_use) { g.order_cur ^= 1; g.order_valid = true; }      // (every launch leaves the flags for the next)
                 ++launches; ++group_launches[k];
@@ -808,7 +830,8 @@ void Engine::advance_launch(long long max_rounds)
     }
     if (streaming) {
         if (tiled) HIP_OK(hipStreamWaitEvent(D.stream, D.tile_t1, 0));
-        auto round = [&](long long c) { launch_stream_round(B, D.any_fluid, D.reb_blocks, D.reb_robot, D.reb_i0, D.stream, c); };
+        const bool sstats = fused ? D.stat_rest : D.stat_all;      // (follows the mask, like the captured graph)
+        auto round = [&](long long c) { launch_stream_round(B, D.any_fluid, D.reb_blocks, D.reb_robot, D.reb_i0, D.stream, c, sstats); };
         long long launched = 0;
         if (opt_.graph_steps > 1 && cap == cap_all && todo >= opt_.graph_steps) {
             if (!D.graph_exec || D.graph_rounds != opt_.graph_steps || D.graph_mask != B.streamed) {
@@ -823,8 +846,8 @@ void Engine::advance_launch(long long max_rounds)
             while (todo - launched >= opt_.graph_steps) { HIP_OK(hipGraphLaunch(D.graph_exec, D.stream)); launched += opt_.graph_steps; }
         }
         for (; launched < todo; ++launched) round(cap);
-        launch_stream_finish(B, D.stream, cap);
-        launches += (D.any_fluid ? 5 : 3) * todo + 1;
+        launch_stream_finish(B, D.stream, cap, sstats);
+        launches += ((D.any_fluid ? 5 : 3) + (sstats ? 1 : 0)) * todo + 1;
     }
     if (fused && !single) for (auto& g : D.groups) HIP_OK(hipStreamWaitEvent(D.stream, g.t1, 0));
     if (tiled) HIP_OK(hipStreamWaitEvent(D.stream, D.tile_t1, 0));
@@ -892,7 +915,21 @@ void Engine::step(long long n)
     auto t0 = std::chrono::steady_clock::now();
     if (robots_.empty() || n <= 0) return;
     if (!prepared_) prepare();
-    advance(n);
+    if (!dev_->any_stat) advance(n);
+    else {
+        // Robots under StopConditionType 4-7 stop when they have settled, which the plan cannot know (its bound is VXH_SETTLE_MAX_STEPS or rule 7's
+        // time): the call goes in pieces of sixteen launches and ends with the piece after which no robot is pending.  A piece boundary is a
+        // launch boundary like any other: the same steps, the same bits.
+        const long long piece = 16LL * std::max(1, opt_.steps_per_launch);
+        for (long long left = n; left > 0;) {
+            const long long k = std::min(left, piece);
+            advance(k);
+            left -= k;
+            bool pending = false;
+            for (size_t r = 0; r < host_.size(); ++r) pending = pending || (robots_[r].nvox > 0 && host_[r].status == VXH_ROBOT_PENDING);
+            if (!pending || rounds_done_ >= dev_->max_planned) break;
+        }
+    }
     counters_.run_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 

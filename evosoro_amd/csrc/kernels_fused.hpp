@@ -81,13 +81,23 @@ struct FusedNoLds {};
 
 // order_in / order_out.  Not COST: the flag words a short launch reads (null: the list order) / those every launch leaves for the next.
 // COST: order_in is the launch's permutation (never null) with the cost words behind it (dispatch_order.hpp order_ws_cost).
-template <int BLOCK, int NACC, bool MESH, bool TABG, bool COST>
+//
+// STATS: the instances that step robots under StopConditionType 4-7 (a robot takes one if and only if its rule is one of them; never COST).
+// The statistics pass rides on the step: every bond lane adds the strain energies of its three slots as it computes them, every voxel lane
+// forms its kinetic energy from the momenta in its registers behind the update, each wavefront reduces the two sums and max |v|^2 (butterfly)
+// and leaves them in the last VXH_STAT_LDS doubles of the dynamic LDS in front of barrier (C); behind it the control lane adds the wavefronts
+// in order, writes the step's entries to the robot's history rings and decides the rule (kernels_physics.hpp stat_*), next to the collision-
+// horizon decision.  Every other instance is compiled without any of it.
+template <int BLOCK, int NACC, bool MESH, bool TABG, bool COST, bool STATS = false>
 __global__ __launch_bounds__(BLOCK, (BLOCK + 255) / 256) void k_robot_steps(DBatch B, const DRobot* __restrict__ robots,
                                                                             const int* __restrict__ robot_list, long long step_cap, int iters,
-                                                                            int lds_doubles, const unsigned long long* __restrict__ order_in,
+                                                                            int lds_doubles_all, const unsigned long long* __restrict__ order_in,
                                                                             unsigned long long* order_out)
 {
     extern __shared__ __align__(16) double lds[];
+    static_assert(!(STATS && (COST || MESH)), "STATS instances: _voxcad robots, no cost measurement");
+    const int lds_doubles = lds_doubles_all - (STATS ? (int)VXH_STAT_LDS : 0);
+    double* const sst = lds + lds_doubles;         // STATS: [3][16] per wavefront kinetic energy, strain energy, max |v|^2 of the step
     double* const ps = lds;
     double* const acc = lds + 8 * BLOCK;
     // the 768-thread MESH variant is SLIM: actuation phases and strains stay in HBM, so that two accumulator tiles and the
@@ -115,6 +125,9 @@ __global__ __launch_bounds__(BLOCK, (BLOCK + 255) / 256) void k_robot_steps(DBat
     const DRobot& R = robots[r];            // separate noalias argument: its loads stay scalar although the kernel stores to HBM
     const unsigned nv = B.nv;
     const int base = R.vox_begin;
+    int sslot = -1;                         // STATS: the robot's history rings
+    DStat Q = {nullptr, nullptr, nullptr};
+    if constexpr (STATS) { Q = stat_tables(B); sslot = __builtin_amdgcn_readfirstlane(Q.stat_slot[r]); }
     const bool valid = tid < R.nvox;
     const int v = base + tid;
     if (tid == 0) { rs = B.rstate[r]; s_na[0] = s_na[1] = s_na[2] = 0; if constexpr (COST) s_cost.reb_sum = s_cost.reb_last = 0u; }
@@ -307,6 +320,8 @@ __global__ __launch_bounds__(BLOCK, (BLOCK + 255) / 256) void k_robot_steps(DBat
             scratch_used = true;
         }
         if (!k_go) break;                      // (the robot has stopped; the last step's trace point, if one was due, is in)
+        StatSamples smp;                       // STATS, control lane: the older sampled entries of the rule's history, requested now, read behind (C)
+        if constexpr (STATS) { if (ctl_thread) smp = stat_prefetch(Q, R, sslot, rs.steps + 1); }
         VXH_T_REB_BEGIN
         if (__builtin_expect(k_rebuild, 0)) {
             if constexpr (COST) { if (tid == 0) s_cost.treb = __builtin_amdgcn_s_memrealtime(); }
@@ -337,15 +352,19 @@ __global__ __launch_bounds__(BLOCK, (BLOCK + 255) / 256) void k_robot_steps(DBat
         // wavefronts, 6 / 5 / 5 / 5 per SIMD -- and its twelve outputs held in registers across the barrier that orders them behind
         // X + Y: the held outputs raise the peak of the bond's register need, 28 -> 124 B of scratch, 25.5 -> 25.9 us per step.)
         bool div = false;
-        fused_round<0, BLOCK, NACC, MESH>(B, R, bct, ps, acc, entry[0], modebits, damp_on, div, st, st_stride);
+        double bond_e = 0;                     // STATS: strain energy of this lane's bonds
+        if constexpr (STATS) fused_round<0, BLOCK, NACC, MESH, true>(B, R, bct, ps, acc, entry[0], modebits, damp_on, div, st, st_stride, &bond_e, Q.bond_energy);
+        else fused_round<0, BLOCK, NACC, MESH>(B, R, bct, ps, acc, entry[0], modebits, damp_on, div, st, st_stride);
         if constexpr (NACC == 1) {
             if (reach_early && wave >= nx) fused_contact_reach_all<BLOCK>(ps, 0, npairs / 3, wave - nx, NWAVES - nx, cmask, rc_code);
             __syncthreads();
         }
-        fused_round<1, BLOCK, NACC, MESH>(B, R, bct, ps, acc, entry[1], modebits, damp_on, div, st, st_stride);
+        if constexpr (STATS) fused_round<1, BLOCK, NACC, MESH, true>(B, R, bct, ps, acc, entry[1], modebits, damp_on, div, st, st_stride, &bond_e, Q.bond_energy);
+        else fused_round<1, BLOCK, NACC, MESH>(B, R, bct, ps, acc, entry[1], modebits, damp_on, div, st, st_stride);
         if constexpr (NACC == 1) { if (reach_early && wave >= ny) fused_contact_reach_all<BLOCK>(ps, npairs / 3, 2 * (npairs / 3), wave - ny, NWAVES - ny, cmask, rc_code); }
         __syncthreads();
-        fused_round<2, BLOCK, NACC, MESH>(B, R, bct, ps, acc, entry[2], modebits, damp_on, div, st, st_stride);
+        if constexpr (STATS) fused_round<2, BLOCK, NACC, MESH, true>(B, R, bct, ps, acc, entry[2], modebits, damp_on, div, st, st_stride, &bond_e, Q.bond_energy);
+        else fused_round<2, BLOCK, NACC, MESH>(B, R, bct, ps, acc, entry[2], modebits, damp_on, div, st, st_stride);
         if (reach_early && wave >= nz) fused_contact_reach_all<BLOCK>(ps, NACC == 1 ? 2 * (npairs / 3) : 0, npairs, wave - nz, NWAVES - nz, cmask, rc_code);
         if (div) s_div = 1;
         VXH_T_MARK(2)
@@ -400,6 +419,11 @@ __global__ __launch_bounds__(BLOCK, (BLOCK + 255) / 256) void k_robot_steps(DBat
         // X / Y chunks with one Y chunk fewer on this wavefront, 25.2 -> 26.0 us per step: that slot is issue-bound on every SIMD; or
         // during the Z slot, which leaves this wavefront idle, 25.3 -> 25.45: the developer timers show this wavefront last at barrier
         // (C), but the voxel wavefronts sharing its SIMD finish at the same time with or without it.)
+        if constexpr (STATS) {                  // the wavefront's share of TotalObjKineticE, TotalObjStrainE and MaxVoxVel^2 (every lane takes part)
+            const double kin_w = wave_sum_fixed(valid ? voxel_kinetic_lin(C, vel2) + voxel_kinetic_ang(C, am) : 0.0);
+            const double str_w = wave_sum_fixed(bond_e), mv_w = wave_max_nonneg(vel2);
+            if ((tid & 63) == 0) { sst[tid >> 6] = kin_w; sst[16 + (tid >> 6)] = str_w; sst[32 + (tid >> 6)] = mv_w; }
+        }
         HorizonInputs hz = {0.0, 0.0, 0, 0, 0, 0};
         if (ctl_thread) { fused_control_begin(R, rs, step_cap, it + 1 < iters, Knext); hz = fused_horizon_prefetch(rs, Knext); }
         if ((R.flags & RF_SELF_COL) && !VXH_DBG(2)) {            // SS.MaxVoxVel for the collision horizon (VX_Sim.cpp:1625-1649)
@@ -414,6 +438,15 @@ __global__ __launch_bounds__(BLOCK, (BLOCK + 255) / 256) void k_robot_steps(DBat
         }
         VXH_T_MARK(5)
         if (ctl_thread) { fused_horizon_decide(R, rs, Knext, hz); s_div = 0; }
+        if constexpr (STATS) {
+            if (ctl_thread) {                  // UpdateStats' sums and histories, then StopConditionMet for the state this step left
+                double kin_e = 0, strain_e = 0, mv2 = 0, move, tot_e;
+                for (int w = 0; w < NWAVES; ++w) { kin_e += sst[w]; strain_e += sst[16 + w]; mv2 = sst[32 + w] > mv2 ? sst[32 + w] : mv2; }
+                stat_push(Q, R, sslot, rs.steps, kin_e, strain_e, mv2, move, tot_e);
+                const double cur = R.stop_type == 4 ? tot_e : (R.stop_type == 5 ? kin_e : move);
+                if (stat_rule_met(R, rs.cur_time, rs.steps, cur, smp)) stat_finish(rs, Knext.go, Knext.flags);
+            }
+        }
         __syncthreads();                       // (A) control + every voxel's published pose visible
         VXH_T_MARK(0)
     }

@@ -696,9 +696,9 @@ __device__ __forceinline__ d3 fused_drag(const DBatch& B, const DRobot& R, const
 
 // A bond of axis A (packed entry of DBatch::bsched: negative-end voxel | positive-end voxel << 10 | class << 20):
 // both poses from the pose tile, history from/to HBM.  Returns the outputs; the caller adds them to the accumulators.
-template <int A, int BLOCK, bool MESH>
+template <int A, int BLOCK, bool MESH, bool ENERGY = false>
 __device__ __forceinline__ BondOut fused_bond(const DBatch& B, const DRobot& R, const DBondClass* bct, const double* ps, int entry,
-                                              unsigned& modebits, bool damp_on, double* st, unsigned st_stride)
+                                              unsigned& modebits, bool damp_on, double* st, unsigned st_stride, const double* energy = nullptr, double* strain_e = nullptr)
 {
     unsigned nv = B.nv;
     asm volatile("" : "+s"(nv));              // plane addresses are rebuilt here by the scalar unit: hoisted out of the step
@@ -719,7 +719,8 @@ __device__ __forceinline__ BondOut fused_bond(const DBatch& B, const DRobot& R, 
     const dq q2 = mkq(ps[4 * BLOCK + l2], ps[5 * BLOCK + l2], ps[6 * BLOCK + l2], ps[7 * BLOCK + l2]);
     // (rotation-vector factor in select form where it was measured faster: the 768-thread variant, 25.15 -> 24.96 us per step; on the
     // 1024-thread one it costs 5 %, dense 10^3 lattices 33.6 -> 35.3 -- same bits either way, kernels_math.hpp rotvec_factor)
-    BondOut o = bond_compute<A, BLOCK == 768>(B, bct[(unsigned)entry >> 20], H, p1, q1, s1, p2, q2, s2, damp_on);
+    BondOut o = ENERGY ? bond_compute<A, BLOCK == 768, ENERGY>(B, bct[(unsigned)entry >> 20], H, p1, q1, s1, p2, q2, s2, damp_on, energy + 3u * ((unsigned)R.btab_begin + ((unsigned)entry >> 20)), strain_e)
+                       : bond_compute<A, BLOCK == 768>(B, bct[(unsigned)entry >> 20], H, p1, q1, s1, p2, q2, s2, damp_on);
     if (H.store_hist) { hrec[0] = make_double2(H.p0, H.p1); hrec[1] = make_double2(H.p2, H.g0); hrec[2] = make_double2(H.g1, H.g2); }
     modebits = (modebits & ~(3u << (2 * A))) | (H.flags << (2 * A));
     if constexpr (MESH) {                     // SetStrainDir (VXS_BondInternal.cpp:300-304): +A side of voxel 1, -A side of voxel 2
@@ -752,15 +753,16 @@ __device__ __forceinline__ void fused_accumulate(double* acc, int l, d3 f, d3 m)
     }
 }
 
-// one axis round: bond, then both ends into the accumulators
-template <int A, int BLOCK, int NACC, bool MESH>
+// one axis round: bond, then both ends into the accumulators (ENERGY: the bond's strain energy is added to the lane's sum)
+template <int A, int BLOCK, int NACC, bool MESH, bool ENERGY = false>
 __device__ __forceinline__ void fused_round(const DBatch& B, const DRobot& R, const DBondClass* bct, const double* ps, double* acc, int entry,
-                                            unsigned& modebits, bool damp_on, bool& div, double* st, unsigned st_stride)
+                                            unsigned& modebits, bool damp_on, bool& div, double* st, unsigned st_stride, double* strain_e = nullptr, const double* energy = nullptr)
 {
     const bool has = entry != -1;
     BondOut o;
     if (has) {
-        o = fused_bond<A, BLOCK, MESH>(B, R, bct, ps, entry, modebits, damp_on, st, st_stride);
+        if constexpr (ENERGY) o = fused_bond<A, BLOCK, MESH, true>(B, R, bct, ps, entry, modebits, damp_on, st, st_stride, energy, strain_e);
+        else o = fused_bond<A, BLOCK, MESH>(B, R, bct, ps, entry, modebits, damp_on, st, st_stride);
         div = div || o.diverged;
         fused_accumulate<BLOCK, false>(acc, entry & 1023, o.f1, o.m1);
     }

@@ -76,9 +76,11 @@ __device__ __forceinline__ void store_bond_hist(const DBatch& B, int slot, const
 // to both orientations): pure arithmetic, `H` in/out.  The outputs are still in the permuted global frame (the caller applies
 // ToOrigDirBond); f2 is only computed for heterogeneous bonds (F2 = -F1 is enforced after the back-rotation otherwise).
 // damp_on = a previous step exists (no damping on the first one, dt == 0 then: VXS_BondInternal.cpp:311).
-template <bool SEL = false>
+// ENERGY (the STATS kernel instances, robots under StopConditionType 4-7): also CVXS_Bond::CalcStrainEnergy (VXS_Bond.cpp:115-121) of the
+// undamped bond-frame forces, as VXS_BondInternal.cpp:156 takes it, ADDED to *strain_e; EC: the class's three factors (DStat::bond_energy).
+template <bool SEL = false, bool ENERGY = false>
 __device__ __forceinline__ BondOut bond_compute_xframe(const DBatch& B, const DBondClass& C, BondHist& H,
-                                                       d3 xrel, dq a1, dq a2, double nom_dist, bool damp_on)
+                                                       d3 xrel, dq a1, dq a2, double nom_dist, bool damp_on, const double* EC = nullptr, double* strain_e = nullptr)
 {
     BondOut o;
     d3 rel = rotinv(a1, xrel);
@@ -145,6 +147,9 @@ __device__ __forceinline__ BondOut bond_compute_xframe(const DBatch& B, const DB
     const double tors = C.a2 * ang2.x;         // a2 (Angle2.x - Angle1.x); Moment1.x is its negative
     d3 m1 = mk3(-tors, C.b2 * pos2.z + C.b3 * (2 * ang1y + ang2.y), -C.b2 * pos2.y + C.b3 * (2 * ang1z + ang2.z));
     d3 m2 = mk3(tors, C.b2 * pos2.z + C.b3 * (ang1y + 2 * ang2.y), -C.b2 * pos2.y + C.b3 * (ang1z + 2 * ang2.z));
+    if constexpr (ENERGY)          // tension + torsion + bending about z and y (b3y == b3z: cubic voxels)
+        *strain_e += EC[0] * f1.x * f1.x + EC[1] * m1.x * m1.x +
+                     EC[2] * ((m1.z * m1.z - m1.z * m2.z + m2.z * m2.z) + (m1.y * m1.y - m1.y * m2.y + m2.y * m2.y));
 
     // velocity damping from the finite-differenced bond-frame pose (AddDampForces :310-346); skipped on the step the
     // mode flips, and the history is only refreshed when it runs
@@ -184,12 +189,12 @@ __device__ __forceinline__ BondOut bond_compute_xframe(const DBatch& B, const DB
 }
 
 // ... along axis A between voxel 1 (negative side) and voxel 2, the axis a compile-time constant (fused and streaming kernels)
-template <int A, bool SEL = false>
+template <int A, bool SEL = false, bool ENERGY = false>
 __device__ __forceinline__ BondOut bond_compute(const DBatch& B, const DBondClass& C, BondHist& H,
                                                 d3 p1, dq q1, double s1, d3 p2, dq q2, double s2,
-                                                bool damp_on)
+                                                bool damp_on, const double* EC = nullptr, double* strain_e = nullptr)
 {
-    BondOut o = bond_compute_xframe<SEL>(B, C, H, to_xdir<A>(p2 - p1), to_xdir<A>(q1), to_xdir<A>(q2), (s1 + s2) * 0.5, damp_on);
+    BondOut o = bond_compute_xframe<SEL, ENERGY>(B, C, H, to_xdir<A>(p2 - p1), to_xdir<A>(q1), to_xdir<A>(q2), (s1 + s2) * 0.5, damp_on, EC, strain_e);
     o.f1 = to_orig<A>(o.f1);
     o.f2 = C.homogeneous ? -o.f1 : to_orig<A>(o.f2);
     o.m1 = to_orig<A>(o.m1);
@@ -199,10 +204,11 @@ __device__ __forceinline__ BondOut bond_compute(const DBatch& B, const DBondClas
 
 // ... the axis a per-lane run-time value (tiled kernel: one flat bond list per tile, all axes in one round).  The same
 // permutations as to_xdir<A> / to_orig<A> written with selects: bit-identical results (negation is exact).
+template <bool ENERGY = false>
 __device__ __forceinline__ BondOut bond_compute_rt(int axis, const DBatch& B, const DBondClass& C, BondHist& H,
-                                                   d3 p1, dq q1, double s1, d3 p2, dq q2, double s2, bool damp_on)
+                                                   d3 p1, dq q1, double s1, d3 p2, dq q2, double s2, bool damp_on, const double* EC = nullptr, double* strain_e = nullptr)
 {
-    BondOut o = bond_compute_xframe(B, C, H, to_xdir_rt(axis, p2 - p1), to_xdir_rt(axis, q1), to_xdir_rt(axis, q2), (s1 + s2) * 0.5, damp_on);
+    BondOut o = bond_compute_xframe<false, ENERGY>(B, C, H, to_xdir_rt(axis, p2 - p1), to_xdir_rt(axis, q1), to_xdir_rt(axis, q2), (s1 + s2) * 0.5, damp_on, EC, strain_e);
     o.f1 = to_orig_rt(axis, o.f1);
     o.f2 = C.homogeneous ? -o.f1 : to_orig_rt(axis, o.f2);
     o.m1 = to_orig_rt(axis, o.m1);
@@ -462,6 +468,78 @@ __device__ __forceinline__ void actuation_sincos(const DRobot& R, double t, doub
     if ((R.flags & RF_TEMP) && t >= R.init_cm_time) sincos((double)(2 * 3.1415926f) * (t / (double)R.temp_period), &s, &c);
 }
 __device__ __forceinline__ double actuation_prenatal_c(const DRobot& R, double t) { return (t >= 0.5 * R.init_cm_time) ? 1.0 : 2 * t / R.init_cm_time; }
+
+// ------------------------------------------------------------------------------------- whole-robot statistics (StopConditionType 4-7)
+__device__ __forceinline__ const DStat& stat_tables(const DBatch& B) { return *stat_address(B); }
+// The statistics pass of the STATS kernel instances: what CVX_Sim::UpdateStats (VX_Sim.cpp:1609-1687) sums over the robot after every step --
+// TotalObjKineticE, TotalObjStrainE, MaxVoxVel -- and pushes onto its three histories.  The headless main leaves StatToCalc at the
+// constructor's CALCSTAT_ALL (VX_Sim.cpp:97; nothing but the GUI loop ever clears it), so all three are recorded for every rule, with and
+// without self-collision, and no entry of a step taken is -1.
+// A lane's share: its voxel's GetCurKineticE (VXS_Voxel.cpp:414-416: 1/2 m |Vel|^2 + 1/2 I |AngVel|^2 of the momenta EulerStep left; the second
+// term as 1/2 AngMom . AngVel, the same to an ulp) ...
+__device__ __forceinline__ double voxel_kinetic_lin(const DVoxClass& C, double vel2) { return 0.5 * C.mass * vel2; }
+__device__ __forceinline__ double voxel_kinetic_ang(const DVoxClass& C, d3 am) { return 0.5 * dot3(am, am * C.inertia_inv); }
+// ... the sums over a (fully active) wavefront as a butterfly: a fixed shape, the same result in every lane.  The workgroup's control lane then
+// adds the wavefronts' values in wavefront order: lanes and wavefronts are the robot's own schedule, so the sums -- not the reference's
+// sequential ones, but only ever compared with thresholds -- are a function of the robot alone, whatever the batch.  No atomics.
+__device__ __forceinline__ double wave_sum_fixed(double v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+// The three entries of the step that raised the step count to `steps` go to the robot's rings (one lane).
+__device__ __forceinline__ void stat_push(const DStat& B, const DRobot& R, int slot, int steps, double kin_e, double strain_e, double maxvel2, double& move, double& tot_e)
+{
+    move = sqrt(maxvel2) * R.dt;          // SS.MaxVoxVel * dt
+    tot_e = kin_e + strain_e;
+    B.stat_ring[stat_entry(slot, VXH_STAT_MOVE, steps)] = move;
+    B.stat_ring[stat_entry(slot, VXH_STAT_KINE, steps)] = kin_e;
+    B.stat_ring[stat_entry(slot, VXH_STAT_TOTE, steps)] = tot_e;
+}
+// The sampled older entries of the rule's plane: history indices 1000, 2000, .. 9000 after the step that raises the count to `steps`.  They were
+// written at least 1000 steps ago, so the control lane requests them at the top of the step and reads them behind it.  Slots no step has written
+// (steps <= 9000) are not read: stat_rule_met answers before it looks at them.
+struct StatSamples { double old[VXH_STAT_SAMPLES]; };
+__device__ __forceinline__ StatSamples stat_prefetch(const DStat& B, const DRobot& R, int slot, int steps)
+{
+    StatSamples s;
+#pragma unroll
+    for (int k = 0; k < VXH_STAT_SAMPLES; ++k)
+        s.old[k] = steps > VXH_STAT_SAMPLES * VXH_STAT_JUMP ? B.stat_ring[stat_entry(slot, stat_plane_of(R.stop_type), steps - (k + 1) * VXH_STAT_JUMP)] : -1.0;
+    return s;
+}
+// CVX_Sim::StopConditionMet for rules 4-7 (VX_Sim.cpp:1402, 1427-1460) after the step that left `steps` and the time t; cur: that step's entry
+// of the rule's plane (history index 0).  numJump = HISTORY_SIZE / 10; fNumVoxInv = 1.0 / (float)NumVox().  Rule 4 compares indices 1000 .. 9000
+// with index 0 -- its abs() is the floating-point one in the reference build (tests/golden/make_stoprule_golden.py) --, rules 5-7 test
+// indices 0 .. 9000; rule 7 tests the time first, without AfterlifeTime, then the motion against MOTION_FLOOR_THR = 5e-08 (VX_Sim.cpp:35).
+__device__ __forceinline__ bool stat_rule_met(const DRobot& R, double t, int steps, double cur, const StatSamples& s)
+{
+    if (t <= R.init_cm_time) return false;
+    if (R.stop_type == 7 && t > R.stop_value) return true;
+    if (steps <= VXH_STAT_SAMPLES * VXH_STAT_JUMP) return false;          // index 9000 still holds the initial -1
+    const double ninv = 1.0 / (double)(float)R.nvox;
+    const double thr = R.stop_type == 7 ? 5e-08 : 0.001 * R.stop_value;
+    bool met = true;
+    if (R.stop_type == 4) {
+#pragma unroll
+        for (int k = 0; k < VXH_STAT_SAMPLES; ++k) met = met && !(fabs(s.old[k] - cur) * ninv > thr);
+    } else {
+        const double f = R.stop_type == 5 ? ninv : 1.0;
+        met = !(cur * f > thr);
+#pragma unroll
+        for (int k = 0; k < VXH_STAT_SAMPLES; ++k) met = met && !(s.old[k] * f > thr);
+    }
+    return met;
+}
+// ... and what the control lane does with the answer behind the step's voxel phase, once step_control_begin has closed the step's accounting
+// (steps, time, trace points) and prepared the next step's control words: a robot that has met its rule is finished and takes no further step;
+// the trace point of the step just taken, if one was due, is still recorded.  `flags`: FusedCtl::flags of the next step (kernels_group.hpp).
+__device__ __forceinline__ void stat_finish(DRobotState& rs, int& go, int& flags)
+{
+    rs.status = 1; rs.active = 0;
+    go = 0; flags &= ~(1 | 2 | 4 | 8);
+}
 
 // ------------------------------------------------------------------------------------- per-robot step control
 // `trace`: mask of the traces that get a point from this step (bit VXH_TRACE_LIFE / _AFTERLIFE / _FROZEN); `trace_index`: entry of the life trace

@@ -1,5 +1,6 @@
 // The streaming kernels, for lattices of any size: k_step_begin / k_mesh_vertices / k_facets / k_bonds / k_voxels, one thread per bond
-// slot / voxel, state and bond outputs through HBM; and k_results, the reduction behind the result file.  Launched by launch_stream.hip.
+// slot / voxel, state and bond outputs through HBM; their variants for batches with robots under StopConditionType 4-7 (k_step_begin_stats,
+// k_bonds_stats, k_stream_stats: the statistics pass of this path); and k_results, the reduction behind the result file.  Launched by launch_stream.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -79,7 +80,12 @@ static __global__ __launch_bounds__(256) void k_results(DBatch B, DResult* __res
     }
 }
 
-static __global__ __launch_bounds__(256) void k_step_begin(DBatch B, long long step_cap, int begin_new_step)
+// STATS (k_step_begin_stats): the batch holds streamed robots under StopConditionType 4-7.  The control thread of such a robot, once it has
+// closed the accounting of the step the previous round computed, takes that step's sums from k_stream_stats, writes the three history entries
+// and decides the rule (kernels_physics.hpp stat_*) -- the same functions of the same step count and time as in the resident kernels.  A robot
+// that has met its rule is finished: no further step, no latch; the trace point of the step just taken is still recorded.
+template <bool STATS>
+__device__ __forceinline__ void stream_step_begin(const DBatch& B, long long step_cap, int begin_new_step)
 {
     const int r = blockIdx.x;
     if (!B.streamed[r]) return;             // (stepped by the resident kernel)
@@ -88,16 +94,32 @@ static __global__ __launch_bounds__(256) void k_step_begin(DBatch B, long long s
     __shared__ double sh[5 * 256];
     __shared__ int s_latch, s_eol, s_trace, s_tidx;
     if (threadIdx.x == 0) {
-        StepCtl c = step_control(R, rs, step_cap, begin_new_step);
+        const int steps_before = rs.steps;
+        StepCtl c = step_control_begin(R, rs, step_cap, begin_new_step);
+        if constexpr (STATS) {
+            const DStat& Q = stat_tables(B);
+            const int slot = Q.stat_slot[r];
+            if (slot >= 0 && rs.status == 0 && rs.steps != steps_before) {      // (a step was finished: its sums are k_stream_stats')
+                const double kin_e = Q.sums[3 * slot], strain_e = Q.sums[3 * slot + 1];
+                double move, tot_e;
+                stat_push(Q, R, slot, rs.steps, kin_e, strain_e, Q.sums[3 * slot + 2], move, tot_e);
+                const double cur = R.stop_type == 4 ? tot_e : (R.stop_type == 5 ? kin_e : move);
+                if (stat_rule_met(R, rs.cur_time, rs.steps, cur, stat_prefetch(Q, R, slot, rs.steps))) { rs.status = 1; rs.active = 0; c.go = c.latch = c.eol = 0; }
+            }
+        }
+        step_control_horizon(R, rs, c, rs.dt_prev);
         s_latch = c.latch; s_eol = c.eol; s_trace = c.trace; s_tidx = c.trace_index;
         if (c.go) actuation_sincos(R, rs.cur_time, rs.act_sin, rs.act_cos);
     }
     __syncthreads();
     if (s_latch || s_eol || s_trace) latch_cm(B, R, rs, PoseFromState{B, rs.steps & 1}, s_latch != 0, s_eol != 0, sh, 256, s_trace, s_tidx);
 }
+static __global__ __launch_bounds__(256) void k_step_begin(DBatch B, long long step_cap, int begin_new_step) { stream_step_begin<false>(B, step_cap, begin_new_step); }
+static __global__ __launch_bounds__(256) void k_step_begin_stats(DBatch B, long long step_cap, int begin_new_step) { stream_step_begin<true>(B, step_cap, begin_new_step); }
 
-template <int A>
-__device__ __forceinline__ void stream_bond(const DBatch& B, const DRobot& R, const DRobotState& rs, int r, int slot, int v1, int bc)
+// ENERGY: also the bond's strain energy, to Q->bond_e[slot] (robots under StopConditionType 4-7)
+template <int A, bool ENERGY = false>
+__device__ __forceinline__ void stream_bond(const DBatch& B, const DRobot& R, const DRobotState& rs, int r, int slot, int v1, int bc, const DStat* Q = nullptr)
 {
     const int v2 = B.nbr[(2 * A) * B.nv + v1];
     const int cur = rs.steps & 1;
@@ -108,7 +130,10 @@ __device__ __forceinline__ void stream_bond(const DBatch& B, const DRobot& R, co
     const double sc1 = SCALE(cur, v1), sc2 = SCALE(cur, v2);
     BondHist H = load_bond_hist(B, slot);
     const unsigned old_flags = H.flags;
-    BondOut o = bond_compute<A>(B, B.bclass_tab[R.btab_begin + bc], H, p1, q1, sc1, p2, q2, sc2, rs.dt_prev != 0);
+    double strain_e = 0;
+    BondOut o = ENERGY ? bond_compute<A, false, ENERGY>(B, B.bclass_tab[R.btab_begin + bc], H, p1, q1, sc1, p2, q2, sc2, rs.dt_prev != 0, Q->bond_energy + 3u * (unsigned)(R.btab_begin + bc), &strain_e)
+                       : bond_compute<A>(B, B.bclass_tab[R.btab_begin + bc], H, p1, q1, sc1, p2, q2, sc2, rs.dt_prev != 0);
+    if constexpr (ENERGY) Q->bond_e[slot] = strain_e;
     store_bond_hist(B, slot, H, old_flags);
     if (o.diverged) atomicOr(&B.rstate[r].diverged, 1);
     if (R.nmv > 0) {      // land_water: CurStrainV1 / CurStrainV2 (SetStrainDir), inputs of the surface mesh in the next step
@@ -175,7 +200,9 @@ static __global__ __launch_bounds__(256) void k_facets(DBatch B)
 
 // blocks [0, bond_blocks): one thread per bond slot; blocks beyond: collision-list rebuilds (reb_robot/reb_i0 tables),
 // which overlap with the bond work of the other robots
-static __global__ __launch_bounds__(256) void k_bonds(DBatch B, int bond_blocks, const int* __restrict__ reb_robot, const int* __restrict__ reb_i0)
+// STATS (k_bonds_stats): the bonds of robots under StopConditionType 4-7 also leave their strain energy (the other robots' bonds take the plain path)
+template <bool STATS>
+__device__ __forceinline__ void stream_bonds(const DBatch& B, int bond_blocks, const int* __restrict__ reb_robot, const int* __restrict__ reb_i0)
 {
     if ((int)blockIdx.x >= bond_blocks) {
         __shared__ double sh[4 * 512 + 256];
@@ -198,10 +225,21 @@ static __global__ __launch_bounds__(256) void k_bonds(DBatch B, int bond_blocks,
     const int bc = B.bclass[tid];
     if (bc < 0) return;
     const DRobot& R = B.robot[r];
+    if constexpr (STATS) {
+        const DStat* Q = &stat_tables(B);
+        if (Q->stat_slot[r] >= 0) {
+            if (axis == 0) stream_bond<0, true>(B, R, rs, r, tid, v1, bc, Q);
+            else if (axis == 1) stream_bond<1, true>(B, R, rs, r, tid, v1, bc, Q);
+            else stream_bond<2, true>(B, R, rs, r, tid, v1, bc, Q);
+            return;
+        }
+    }
     if (axis == 0) stream_bond<0>(B, R, rs, r, tid, v1, bc);
     else if (axis == 1) stream_bond<1>(B, R, rs, r, tid, v1, bc);
     else stream_bond<2>(B, R, rs, r, tid, v1, bc);
 }
+static __global__ __launch_bounds__(256) void k_bonds(DBatch B, int bond_blocks, const int* __restrict__ reb_robot, const int* __restrict__ reb_i0) { stream_bonds<false>(B, bond_blocks, reb_robot, reb_i0); }
+static __global__ __launch_bounds__(256) void k_bonds_stats(DBatch B, int bond_blocks, const int* __restrict__ reb_robot, const int* __restrict__ reb_i0) { stream_bonds<true>(B, bond_blocks, reb_robot, reb_i0); }
 
 static __global__ __launch_bounds__(256) void k_voxels(DBatch B)
 {
@@ -262,6 +300,41 @@ static __global__ __launch_bounds__(256) void k_voxels(DBatch B)
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) { double o = __shfl_xor(vel2, off); vel2 = o > vel2 ? o : vel2; }
         if ((threadIdx.x & 63) == 0) atomicMax(&rs.maxvel2_bits, (unsigned long long)__double_as_longlong(vel2));
+    }
+}
+
+// The statistics pass of the streaming path, behind k_voxels: one workgroup per streamed robot under StopConditionType 4-7 (the others leave at
+// once).  Thread t takes voxels t, t + 256, ... in order: the voxel's kinetic energy from the momenta k_voxels stored (the very expressions of
+// the resident kernels: |lm / m|^2 is what voxel_update returns), the strain energies its three positive-side bond slots left in DStat::bond_e,
+// and |v|^2 for the maximum.  Wavefronts reduce with the fixed butterfly, thread 0 adds the four of them in order: a shape the robot alone
+// decides, no atomics.  The sums go to DStat::sums; the next k_step_begin_stats writes the histories and decides the rule.
+static __global__ __launch_bounds__(256) void k_stream_stats(DBatch B)
+{
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const DStat& Q = stat_tables(B);
+    const int slot = Q.stat_slot[r];
+    if (slot < 0 || !B.streamed[r]) return;
+    const DRobot& R = B.robot[r];
+    const DRobotState& rs = B.rstate[r];
+    if (!rs.active || rs.diverged) return;     // (no step was taken: k_voxels' own condition)
+    __shared__ double red[3][4];
+    double kin_e = 0, strain_e = 0, mv2 = 0;
+    for (int k = tid; k < R.nvox; k += 256) {
+        const int v = R.vox_begin + k;
+        const DVoxClass& C = B.vclass_tab[R.vtab_begin + B.vclass[v]];
+        const double vel2 = len2(mk3(LINMOM(0, v), LINMOM(1, v), LINMOM(2, v)) * C.mass_inv);
+        kin_e += voxel_kinetic_lin(C, vel2) + voxel_kinetic_ang(C, mk3(ANGMOM(0, v), ANGMOM(1, v), ANGMOM(2, v)));
+        mv2 = vel2 > mv2 ? vel2 : mv2;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) if (B.bclass[a * B.nv + v] >= 0) strain_e += Q.bond_e[a * B.nv + v];
+    }
+    kin_e = wave_sum_fixed(kin_e); strain_e = wave_sum_fixed(strain_e); mv2 = wave_max_nonneg(mv2);
+    if ((tid & 63) == 0) { red[0][tid >> 6] = kin_e; red[1][tid >> 6] = strain_e; red[2][tid >> 6] = mv2; }
+    __syncthreads();
+    if (tid == 0) {
+        double k4 = 0, s4 = 0, m4 = 0;
+        for (int w = 0; w < 4; ++w) { k4 += red[0][w]; s4 += red[1][w]; m4 = red[2][w] > m4 ? red[2][w] : m4; }
+        Q.sums[3 * slot] = k4; Q.sums[3 * slot + 1] = s4; Q.sums[3 * slot + 2] = m4;
     }
 }
 

@@ -35,9 +35,9 @@ namespace vxh {
 // (VXH_WIDE_REC, VXH_WIDE_STATIC_LDS: device_types.hpp, the host sizes the launch with them)
 
 // bond `entry` of the combined list: poses from the pose tile, history from / to HBM (L2), outputs into record `slot`
-template <int BLOCK, bool MESH>
+template <int BLOCK, bool MESH, bool ENERGY = false>
 __device__ __forceinline__ bool wide_bond(const DBatch& B, const DRobot& R, const DBondClass* bct, const double* ps, double* rec, int entry, int slot,
-                                          unsigned& modebits, int shift, bool damp_on, double* st)
+                                          unsigned& modebits, int shift, bool damp_on, double* st, double* strain_e = nullptr, const double* energy = nullptr)
 {
     unsigned nv = B.nv;
     asm volatile("" : "+s"(nv));              // (plane addresses rebuilt per bond by the scalar unit, see fused_bond)
@@ -53,7 +53,9 @@ __device__ __forceinline__ bool wide_bond(const DBatch& B, const DRobot& R, cons
     const d3 p2 = mk3(ps[l2], ps[BLOCK + l2], ps[2 * BLOCK + l2]);
     const double s2 = ps[3 * BLOCK + l2];
     const dq q2 = mkq(ps[4 * BLOCK + l2], ps[5 * BLOCK + l2], ps[6 * BLOCK + l2], ps[7 * BLOCK + l2]);
-    const BondOut o = bond_compute_rt(axis, B, bct[(unsigned)entry >> 20], H, p1, q1, s1, p2, q2, s2, damp_on);
+    // (STATS instances: the bond's strain energy joins the lane's sum)
+    const BondOut o = ENERGY ? bond_compute_rt<ENERGY>(axis, B, bct[(unsigned)entry >> 20], H, p1, q1, s1, p2, q2, s2, damp_on, energy + 3u * ((unsigned)R.btab_begin + ((unsigned)entry >> 20)), strain_e)
+                             : bond_compute_rt(axis, B, bct[(unsigned)entry >> 20], H, p1, q1, s1, p2, q2, s2, damp_on);
     if (H.store_hist) { hrec[0] = make_double2(H.p0, H.p1); hrec[1] = make_double2(H.p2, H.g0); hrec[2] = make_double2(H.g1, H.g2); }
     modebits = (modebits & ~(3u << shift)) | (H.flags << shift);
     if constexpr (MESH) {                     // SetStrainDir (VXS_BondInternal.cpp:300-304): +A side of voxel 1, -A side of voxel 2
@@ -83,12 +85,20 @@ __device__ __forceinline__ d3 wide_gather(const double* rec, int g0, int g1, int
     return acc;
 }
 
-template <int BLOCK, bool MESH, bool TABG>
+// STATS: the instances for robots under StopConditionType 4-7, as in k_robot_steps (kernels_fused.hpp): bond lanes add their strain energies, the
+// two halves of a voxel's update their halves of its kinetic energy (a split robot's on different wavefronts: the sum does not care), every
+// wavefront leaves its sums and max |v|^2 in the last VXH_STAT_LDS doubles of the dynamic LDS in front of barrier (X), and behind it the control
+// lane writes the history rings and decides the rule -- in front of one more barrier, because here EVERY thread reads the next step's control
+// words right behind (X).
+template <int BLOCK, bool MESH, bool TABG, bool STATS = false>
 __global__ __launch_bounds__(BLOCK, BLOCK / 256) void k_robot_wide(DBatch B, const DRobot* __restrict__ robots,
                                                                    const int* __restrict__ robot_list, long long step_cap, int iters,
-                                                                   int lds_doubles_all, int two_tiles)
+                                                                   int lds_doubles_given, int two_tiles)
 {
     extern __shared__ __align__(16) double lds[];
+    static_assert(!(STATS && MESH), "STATS instances: _voxcad robots");
+    const int lds_doubles_all = lds_doubles_given - (STATS ? (int)VXH_STAT_LDS : 0);
+    double* const sst = lds + lds_doubles_all;     // STATS: [3][16] per wavefront kinetic energy, strain energy, max |v|^2 of the step
     // two_tiles: a second pose tile at the end of the dynamic LDS (the host grants it where the robot's layout leaves 8 * BLOCK
     // doubles: every walker, the smaller swimmers).  The new poses then go into the OTHER tile during the voxel phase -- nobody reads
     // it -- and the step has two workgroup barriers instead of three (see the step loop).
@@ -112,6 +122,9 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void k_robot_wide(DBatch B, con
     const DRobot& R = robots[r];
     const unsigned nv = B.nv;
     const int base = R.vox_begin, nvox = R.nvox;
+    int sslot = -1;                           // STATS: the robot's history rings
+    DStat Q = {nullptr, nullptr, nullptr};
+    if constexpr (STATS) { Q = stat_tables(B); sslot = __builtin_amdgcn_readfirstlane(Q.stat_slot[r]); }
     // roles of this thread: the translation of voxel `tid` (valid), the rotation + size of voxel `la` (angr); the same voxel unless the
     // robot is small enough to give the two halves to different wavefronts
     const bool split = 2 * nvox <= BLOCK;
@@ -260,6 +273,8 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void k_robot_wide(DBatch B, con
         if (k_latch || k_eol || k_trace)
             fused_latch_cm<BLOCK>(B, R, rs, ps, rec, valid, Cl, k_latch, k_eol, fused_trace_mask(kf), K.trace_index);
         if (!k_go) break;
+        StatSamples smp;                       // STATS, control lane: the older sampled entries of the rule's history, requested now, read behind (X)
+        if constexpr (STATS) { if (ctl_thread) smp = stat_prefetch(Q, R, sslot, rs.steps + 1); }
         if (__builtin_expect(k_rebuild, 0)) {
             fused_rebuild<BLOCK>(B, R, rs, ps, rec, 12 * BLOCK, (double*)cmask, max(0, lds_doubles - (int)((double*)cmask - lds)), vct);
             rows_to_lds();
@@ -273,8 +288,14 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void k_robot_wide(DBatch B, con
 
         // ---- bond phase: every bond of the robot, all axes, one round (two for the threads that hold a second entry)
         bool div = false;
-        if (e0 != -1) div = wide_bond<BLOCK, MESH>(B, R, bct, ps, rec, e0, tid, modebits, 0, damp_on, st);
-        if (e1 != -1) div = wide_bond<BLOCK, MESH>(B, R, bct, ps, rec, e1, tid + BLOCK, modebits, 2, damp_on, st) || div;
+        double bond_e = 0;                     // STATS: strain energy of this lane's bonds
+        if constexpr (STATS) {
+            if (e0 != -1) div = wide_bond<BLOCK, MESH, true>(B, R, bct, ps, rec, e0, tid, modebits, 0, damp_on, st, &bond_e, Q.bond_energy);
+            if (e1 != -1) div = wide_bond<BLOCK, MESH, true>(B, R, bct, ps, rec, e1, tid + BLOCK, modebits, 2, damp_on, st, &bond_e, Q.bond_energy) || div;
+        } else {
+            if (e0 != -1) div = wide_bond<BLOCK, MESH>(B, R, bct, ps, rec, e0, tid, modebits, 0, damp_on, st);
+            if (e1 != -1) div = wide_bond<BLOCK, MESH>(B, R, bct, ps, rec, e1, tid + BLOCK, modebits, 2, damp_on, st) || div;
+        }
         if (reach_early && wave >= nbw) fused_contact_reach_all<BLOCK>(ps, 0, npairs, wave - nbw, NWAVES - nbw, cmask, rc_code);
         if (div) s_divf[par] = 1;
         VXH_T_MARK(2)
@@ -314,6 +335,11 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void k_robot_wide(DBatch B, con
             ang = mkq(ps[4 * BLOCK + la], ps[5 * BLOCK + la], ps[6 * BLOCK + la], ps[7 * BLOCK + la]);
             voxel_update_ang(B, R, Ca, vva, K.time, K.act_sin, K.act_cos, K.prenatal_c, M, am, ang, scale_a, ph_sin, ph_cos, amp_damp);
         }
+        if constexpr (STATS) {                  // the wavefront's share of TotalObjKineticE, TotalObjStrainE and MaxVoxVel^2 (every lane takes part)
+            const double kin_w = wave_sum_fixed((valid ? voxel_kinetic_lin(Cl, vel2) : 0.0) + (angr ? voxel_kinetic_ang(Ca, am) : 0.0));
+            const double str_w = wave_sum_fixed(bond_e), mv_w = wave_max_nonneg(vel2);
+            if ((tid & 63) == 0) { sst[tid >> 6] = kin_w; sst[16 + (tid >> 6)] = str_w; sst[32 + (tid >> 6)] = mv_w; }
+        }
         if (ctl_thread) { fused_control_begin(R, rs, step_cap, it + 1 < iters, Knext); s_divf[par ^ 1] = 0; }   // next step's control, off the critical path
         if (R.flags & RF_SELF_COL) {             // SS.MaxVoxVel for the collision horizon (VX_Sim.cpp:1625-1649)
             vel2 = wave_max_nonneg(vel2);
@@ -330,6 +356,16 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void k_robot_wide(DBatch B, con
         VXH_T_MARK(4)
         __syncthreads();                       // (X) the voxel phase is complete: max |v|^2 in, the next step's control block written
         if (!two_tiles) store_poses();         // (every read of the old poses is done)
+        if constexpr (STATS) {
+            if (ctl_thread) {                  // UpdateStats' sums and histories, then StopConditionMet for the state this step left
+                double kin_e = 0, strain_e = 0, mv2 = 0, move, tot_e;
+                for (int w = 0; w < NWAVES; ++w) { kin_e += sst[w]; strain_e += sst[16 + w]; mv2 = sst[32 + w] > mv2 ? sst[32 + w] : mv2; }
+                stat_push(Q, R, sslot, rs.steps, kin_e, strain_e, mv2, move, tot_e);
+                const double cur = R.stop_type == 4 ? tot_e : (R.stop_type == 5 ? kin_e : move);
+                if (stat_rule_met(R, rs.cur_time, rs.steps, cur, smp)) stat_finish(rs, Knext.go, Knext.flags);
+            }
+            __syncthreads();                   // the next step's control words are final
+        }
         VXH_T_MARK(5)
         // the collision-horizon update of the NEXT step (step_control_horizon, kernels_physics.hpp), by every thread for itself
         {

@@ -33,21 +33,23 @@ inline void grant_dynamic_lds(const void* kernel, size_t (&granted)[64], size_t 
 // k_robot_steps<block, nacc, FLUID, TABG, COST> (kernels_fused.hpp): block in {256, 512, 768, 1024}; land robots / land_water robots;
 // cost: the instances that measure what their robots cost (order_in: the launch's permutation with the cost words behind it, never null)
 void launch_fused_land(const DBatch& B, int block, bool tabg, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters,
-                       const unsigned long long* order_in, unsigned long long* order_out, bool cost);
+                       const unsigned long long* order_in, unsigned long long* order_out, bool cost, bool stats = false);
 void launch_fused_mesh(const DBatch& B, int block, bool tabg, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters,
                        const unsigned long long* order_in, unsigned long long* order_out, bool cost);
-// k_robot_wide<512, MESH, TABG> (kernels_wide.hpp)
-void launch_wide_group(const DBatch& B, bool mesh, bool tabg, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters, int two_tiles);
+// k_robot_wide<512, MESH, TABG, STATS> (kernels_wide.hpp); stats (with launch_fused_land too): the STATS instances, for groups of robots under
+// StopConditionType 4-7
+void launch_wide_group(const DBatch& B, bool mesh, bool tabg, bool stats, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters, int two_tiles);
 // k_tile_steps<TABG, MESH, FLUID> (kernels_tiled.hpp); mesh_kind: 0 = _voxcad, 1 = land_water robot on land, 2 = in a fluid
 // small: every tile of the launch within VXH_TILE_S_OWN / _HALO / _BONDS (device_types.hpp): the instances with compile-time LDS strides
 void launch_tile_group(const DBatch& B, bool tabg, int mesh_kind, bool small, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters, unsigned gen);
 // threads of a tile's workgroup (the host sizes launches and LDS with the kernel's own constants)
 int tile_threads();
 // the streaming kernels (kernels_stream.hpp).  One time step of the streamed robots: k_step_begin, k_mesh_vertices and k_facets when any robot is
-// in a fluid, k_bonds (its blocks + reb_blocks broad-phase blocks: reb_robot / reb_i0), k_voxels ...
-void launch_stream_round(const DBatch& B, bool any_fluid, int reb_blocks, const int* reb_robot, const int* reb_i0, hipStream_t s, long long cap);
+// in a fluid, k_bonds (its blocks + reb_blocks broad-phase blocks: reb_robot / reb_i0), k_voxels; stats: a streamed robot is under
+// StopConditionType 4-7 -- k_step_begin_stats and k_bonds_stats in their places, k_stream_stats behind k_voxels ...
+void launch_stream_round(const DBatch& B, bool any_fluid, int reb_blocks, const int* reb_robot, const int* reb_i0, hipStream_t s, long long cap, bool stats);
 // ... and the k_step_begin that finishes the last step of a call
-void launch_stream_finish(const DBatch& B, hipStream_t s, long long cap);
+void launch_stream_finish(const DBatch& B, hipStream_t s, long long cap, bool stats);
 // k_results: one DResult per robot
 void launch_results(const DBatch& B, int n_robots, DResult* out, hipStream_t s);
 // k_shape_results (kernels_shape.hpp): one workgroup per robot of Q.list (count of them); lds: shape_lds_bytes of the largest

@@ -2,25 +2,32 @@
 #include "kernels_stream.hpp"
 #include "kernels_order.hpp"
 #include "launch.hpp"
+#include <stdexcept>
 
 namespace vxh {
 
-// one time step of the streamed robots: five kernels when a robot is in a fluid, else three
-void launch_stream_round(const DBatch& B, bool any_fluid, int reb_blocks, const int* reb_robot, const int* reb_i0, hipStream_t s, long long cap)
+// one time step of the streamed robots: five kernels when a robot is in a fluid, else three; stats: some streamed robot is under
+// StopConditionType 4-7 -- the _stats variants of k_step_begin and k_bonds, and the reduction k_stream_stats behind k_voxels
+void launch_stream_round(const DBatch& B, bool any_fluid, int reb_blocks, const int* reb_robot, const int* reb_i0, hipStream_t s, long long cap, bool stats)
 {
     const int nb_b = (3 * B.nv + 255) / 256, nb_v = (B.nv + 255) / 256;
-    hipLaunchKernelGGL(k_step_begin, dim3(B.n_robots), dim3(256), 0, s, B, cap, 1);
+    if (stats && B.stat_lo == 0 && B.stat_hi == 0) throw std::runtime_error("streaming statistics pass without history rings");
+    if (stats) hipLaunchKernelGGL(k_step_begin_stats, dim3(B.n_robots), dim3(256), 0, s, B, cap, 1);
+    else hipLaunchKernelGGL(k_step_begin, dim3(B.n_robots), dim3(256), 0, s, B, cap, 1);
     if (any_fluid) {
         hipLaunchKernelGGL(k_mesh_vertices, dim3((B.n_mv + 255) / 256), dim3(256), 0, s, B);
         hipLaunchKernelGGL(k_facets, dim3((B.n_facet + 255) / 256), dim3(256), 0, s, B);
     }
-    hipLaunchKernelGGL(k_bonds, dim3(nb_b + reb_blocks), dim3(256), 0, s, B, nb_b, reb_robot, reb_i0);
+    if (stats) hipLaunchKernelGGL(k_bonds_stats, dim3(nb_b + reb_blocks), dim3(256), 0, s, B, nb_b, reb_robot, reb_i0);
+    else hipLaunchKernelGGL(k_bonds, dim3(nb_b + reb_blocks), dim3(256), 0, s, B, nb_b, reb_robot, reb_i0);
     hipLaunchKernelGGL(k_voxels, dim3(nb_v), dim3(256), 0, s, B);
+    if (stats) hipLaunchKernelGGL(k_stream_stats, dim3(B.n_robots), dim3(256), 0, s, B);
 }
 
-void launch_stream_finish(const DBatch& B, hipStream_t s, long long cap)
+void launch_stream_finish(const DBatch& B, hipStream_t s, long long cap, bool stats)
 {
-    hipLaunchKernelGGL(k_step_begin, dim3(B.n_robots), dim3(256), 0, s, B, cap, 0);   // finish the last step
+    if (stats) hipLaunchKernelGGL(k_step_begin_stats, dim3(B.n_robots), dim3(256), 0, s, B, cap, 0);   // finish the last step
+    else hipLaunchKernelGGL(k_step_begin, dim3(B.n_robots), dim3(256), 0, s, B, cap, 0);
 }
 
 void launch_results(const DBatch& B, int n_robots, DResult* out, hipStream_t s)

@@ -4,17 +4,22 @@
 
 namespace vxh {
 
-template <int BLOCK, bool MESH, bool TABG>
+template <int BLOCK, bool MESH, bool TABG, bool STATS = false>
 static void launch_wide(const DBatch& B, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters, int two_tiles)
 {
     static size_t granted[64] = {};
-    grant_dynamic_lds((const void*)k_robot_wide<BLOCK, MESH, TABG>, granted, lds);
-    hipLaunchKernelGGL((k_robot_wide<BLOCK, MESH, TABG>), dim3(count), dim3(BLOCK), lds, s, B, B.robot, list, cap, iters, (int)(lds / 8), two_tiles);
+    grant_dynamic_lds((const void*)k_robot_wide<BLOCK, MESH, TABG, STATS>, granted, lds);
+    hipLaunchKernelGGL((k_robot_wide<BLOCK, MESH, TABG, STATS>), dim3(count), dim3(BLOCK), lds, s, B, B.robot, list, cap, iters, (int)(lds / 8), two_tiles);
 }
 
-void launch_wide_group(const DBatch& B, bool mesh, bool tabg, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters, int two_tiles)
+// stats: the group's robots are under StopConditionType 4-7 (_voxcad only; lds includes the VXH_STAT_LDS doubles of the pass)
+void launch_wide_group(const DBatch& B, bool mesh, bool tabg, bool stats, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters, int two_tiles)
 {
-    if (mesh) { if (tabg) launch_wide<512, true, true>(B, list, count, lds, s, cap, iters, two_tiles); else launch_wide<512, true, false>(B, list, count, lds, s, cap, iters, two_tiles); }
+    if (stats) {
+        if (mesh || (B.stat_lo == 0 && B.stat_hi == 0)) throw std::runtime_error("k_robot_wide: a STATS group without history rings or with a surface mesh");
+        if (tabg) launch_wide<512, false, true, true>(B, list, count, lds, s, cap, iters, two_tiles); else launch_wide<512, false, false, true>(B, list, count, lds, s, cap, iters, two_tiles);
+    }
+    else if (mesh) { if (tabg) launch_wide<512, true, true>(B, list, count, lds, s, cap, iters, two_tiles); else launch_wide<512, true, false>(B, list, count, lds, s, cap, iters, two_tiles); }
     else { if (tabg) launch_wide<512, false, true>(B, list, count, lds, s, cap, iters, two_tiles); else launch_wide<512, false, false>(B, list, count, lds, s, cap, iters, two_tiles); }
 }
 

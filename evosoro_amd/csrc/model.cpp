@@ -118,6 +118,10 @@ bool stop_met(const VxaModel& m, double t, long long steps)
     case 1: return steps > (long long)(int)(m.stop_value + 0.5);
     case 2: return m.variant == 0 ? t > (m.stop_value + m.afterlife_time) : t > m.stop_value;
     case 3: return t > m.temp_period * m.stop_value;
+    // the energy and motion rules end when the robot has settled, which only the run can tell: the plan is an upper bound -- rule 7's
+    // own time bound, for rules 4-6 the step budget of model.hpp
+    case 4: case 5: case 6: return steps >= VXH_SETTLE_MAX_STEPS;
+    case 7: return t > m.stop_value;
     default: return false;
     }
 }

@@ -91,6 +91,9 @@ struct TilePlan {
 // k_request tiles or somewhat fewer (a k without a good factorisation into a grid is replaced by a smaller one with one)
 TilePlan plan_tiles(const RobotModel& model, int k_request);
 
+// StopConditionType 4-6 (total energy constant, kinetic energy low, largest move small: VX_Sim.cpp:1427-1448) have no bound of their own;
+// a robot that has not settled after this many steps is left VXH_ROBOT_PENDING (the reference would step it forever)
+constexpr long long VXH_SETTLE_MAX_STEPS = 1000000;
 // number of TimeStep calls until StopConditionMet, replaying CurTime += dt in double precision
 long long plan_steps(const VxaModel& vxa, double dt);
 

@@ -234,7 +234,11 @@ VxaModel read_vxa(const char* data, size_t len, int variant)
         if (const XmlNode* f = ga->child("CurvaturesTmpFile")) m.curvatures_tmp_file = f->text;
     }
     m.want_mesh = m.variant == 1;
-    if (!(m.stop_type >= 0 && m.stop_type <= 3)) m.unsupported.push_back("StopConditionType>3");
+    // 0 none, 1 time steps, 2 simulated time, 3 actuation periods; 4-7 the energy and motion rules of CVX_Sim::StopConditionMet
+    // (VX_Sim.cpp:1427-1460), _voxcad only: LW/VX_Sim.cpp:1163-1202 has no rule 7, evaluates rules 4-6 before InitCmTime too and so
+    // is another rule set, not stepped here.  8 (SC_POINTING_ERR) and above: sources, refused.
+    if (!(m.stop_type >= 0 && m.stop_type <= 7)) m.unsupported.push_back("StopConditionType " + std::to_string(m.stop_type) + " (supported: 0-7)");
+    else if (m.stop_type > 3 && variant == 1) m.unsupported.push_back("StopConditionType " + std::to_string(m.stop_type) + " in the land_water simulator (energy and motion stop rules: _voxcad only)");
 
     // ---- Environment (VX_Environment.cpp:123-234; LW/VX_Environment.cpp:190-191)
     auto count_regions = [&](const char* block, const char* counter) {

@@ -121,7 +121,11 @@ typedef struct vxh_counters {
 
 /* Host-only view of what Import() would build for a .vxa (no device needed): voxel/bond/surface counts in the
  * reference's ordering, OptimalDt (CalcMaxDt, VX/VX_Sim.cpp:1693-1727), dt = DtFrac*OptimalDt and the number of
- * TimeStep() calls the reference main loop would make (voxelyzeMain/main.cpp:89-111 with StopConditionMet). */
+ * TimeStep() calls the reference main loop would make (voxelyzeMain/main.cpp:89-111 with StopConditionMet).
+ * StopConditionType 0 none (refused: never ends), 1 time steps, 2 simulated time, 3 actuation periods: the exact count.  4 total energy
+ * constant, 5 kinetic energy low, 6 largest voxel move small, 7 largest move below the floor threshold or time up (_voxcad only): the robot
+ * stops when it has settled, and planned_steps is an upper bound -- rule 7's time, 1000000 steps for rules 4-6, after which a robot that
+ * has not settled is left VXH_ROBOT_PENDING.  8 and above: VXH_ERR_UNSUPPORTED. */
 typedef struct vxh_model_info {
     int nvox, nbond, nsurf, n_vox_classes, n_bond_classes, reserved;
     double opt_dt, dt;

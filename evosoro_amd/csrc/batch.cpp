@@ -13,18 +13,59 @@
 
 namespace vxh {
 
-WideLayout wide_layout(const RobotModel& M, int variant)
+namespace {
+// record region of a wide-kernel robot whose voxel planes have `plane` slots (the scratch of the whole-robot passes is 12 planes)
+WideLayout wide_layout_of(const RobotModel& M, int variant, int plane)
 {
     WideLayout W;
     const bool in_fluid = variant == 1 && M.vxa.fluid_env;
-    const int scratch = 12 * WIDE_BLOCK + (in_fluid ? 3 * ((M.nvox + 63) / 64 * 64) + 3 * M.nmv : 0);
+    const int scratch = 12 * plane + (in_fluid ? 3 * ((M.nvox + 63) / 64 * 64) + 3 * M.nmv : 0);
     W.zidx = std::max(M.nbond, (scratch + VXH_WIDE_REC - 1) / VXH_WIDE_REC);
     W.region = (VXH_WIDE_REC * (W.zidx + 1) + 1) & ~1;
     return W;
 }
+}  // namespace
+
 bool wide_listed(const RobotModel& M, int variant, const Options& opt)
 {
-    return opt.wide && M.nvox > 0 && M.nvox <= WIDE_BLOCK && M.nbond <= 1023 && M.bond_classes.size() <= 4095 && wide_layout(M, variant).zidx <= 1023;
+    return opt.wide && M.nvox > 0 && M.nvox <= WIDE_BLOCK && M.nbond <= 1023 && M.bond_classes.size() <= 4095 && wide_layout_of(M, variant, WIDE_BLOCK).zidx <= 1023;
+}
+
+// The small instances (k_robot_wide<VXH_WIDE_SMALL_BLOCK, ..>, option wide_small) and their LDS, laid out as the top of the kernel lays it
+// out with planes of VXH_WIDE_SMALL_VOX slots: pose tile, record region, class tables (unless TABG), strain tile of a land_water robot,
+// contact mask and contact rows.  The rows are part of the need -- the instance exists so that several workgroups share a CU, and a robot
+// that wants more than its share of the LDS keeps the 512-thread instance, which has a CU to itself: 12 bytes per partner, every surface
+// voxel's row as long as the option col_cap lets it grow (the reach mask of a row has 64 bits; longer rows stay in memory); without a cap rows
+// are as long as the physics makes them, nearly all a few partners, and the pool is 8 KB or the full rows if those are smaller, what the
+// 512-thread layout asks for at least (rows that do not fit are read from memory, wavefront by wavefront: same arithmetic, same order).
+WideSmall wide_small(const RobotModel& M, int variant, const Options& opt)
+{
+    WideSmall S;
+    if (!opt.wide_small || !wide_listed(M, variant, opt) || M.nvox > VXH_WIDE_SMALL_VOX || stat_rules(M)) return S;
+    const size_t budget = (((size_t)160 * 1024 / VXH_WIDE_SMALL_PER_CU) & ~(size_t)7) - VXH_WIDE_SMALL_STATIC_LDS;
+    const WideLayout W = wide_layout_of(M, variant, VXH_WIDE_SMALL_VOX);
+    const int mesh = M.nmv > 0 ? 1 : 0;
+    size_t rows = 0;
+    if (M.vxa.self_col_enabled) {
+        const size_t full = (size_t)12 * M.nsurf * std::min(std::max(M.nsurf - 1, 1), 64);
+        rows = opt.col_cap > 0 ? (size_t)12 * M.nsurf * std::min(std::min(opt.col_cap, std::max(M.nsurf - 1, 1)), 64) : std::min<size_t>(full, 8 * 1024);
+        rows += 8 * VXH_WIDE_SMALL_VOX + 16;      // (the mask; the pool's rounding in the kernel)
+    }
+    auto need = [&](bool tables_in_lds) {
+        return (size_t)(8 * VXH_WIDE_SMALL_VOX + W.region) * 8 + (tables_in_lds ? M.bond_classes.size() * sizeof(DBondClass) + M.vox_classes.size() * sizeof(DVoxClass) : 0) +
+               (mesh ? (size_t)48 * VXH_WIDE_SMALL_VOX : 0) + rows;
+    };
+    const int tabg = need(true) > budget ? 1 : 0;
+    if (need(!tabg) > budget) return S;
+    S.taken = 1; S.tabg = tabg; S.lds = (need(!tabg) + 7) & ~(size_t)7;
+    const size_t tile = (size_t)64 * VXH_WIDE_SMALL_VOX;
+    if (opt.wide_two_tiles && S.lds + tile <= budget) { S.two_tiles = 1; S.lds += tile; }
+    return S;
+}
+
+WideLayout wide_layout(const RobotModel& M, int variant, const Options& opt)
+{
+    return wide_layout_of(M, variant, wide_small(M, variant, opt).taken ? (int)VXH_WIDE_SMALL_VOX : WIDE_BLOCK);
 }
 int resident_block(int n) { return n <= 256 ? 256 : (n <= 512 ? 512 : (n <= 768 ? 768 : 1024)); }
 
@@ -38,10 +79,14 @@ FusedVariant fused_variant(const RobotModel& M, int variant, const Options& opt)
     fv.stats = stat_rules(M) ? 1 : 0;
     const size_t stat_lds = fv.stats ? (size_t)8 * VXH_STAT_LDS : 0;
     if (n == 0 || n > 1024 || M.bond_classes.size() > 4095) return fv;   // (12 class bits in a bond entry; a robot of 1024 voxels has at most 3072 bonds)
+    if (const WideSmall S = wide_small(M, variant, opt); S.taken) {
+        fv.block = VXH_WIDE_SMALL_BLOCK; fv.nacc = 0; fv.fluid = M.nmv > 0 ? 1 : 0; fv.tabg = S.tabg; fv.wide = 1; fv.two_tiles = S.two_tiles; fv.lds = S.lds;
+        return fv;
+    }
     if (wide_listed(M, variant, opt)) {
         // the wide kernel when its LDS layout fits (mirrors the top of k_robot_wide): pose tile, record region, class tables,
         // the strain tile of a land_water robot, the mask + pool of the contact rows
-        const WideLayout W = wide_layout(M, variant);
+        const WideLayout W = wide_layout_of(M, variant, WIDE_BLOCK);
         const int mesh = M.nmv > 0 ? 1 : 0;
         auto wneed = [&](bool tables_in_lds) {
             return (size_t)(8 * WIDE_BLOCK + W.region) * 8 + stat_lds +
@@ -408,7 +453,7 @@ void wide_lists(const RobotModel& M, int r, int variant, const Options& opt, Hos
     if (!wide_listed(M, variant, opt)) return;
     // wide kernel: all bonds in one list, axis after axis; a bond's place in it is the number of its record, and every voxel
     // learns the records of its six directions (+A: the bond it is the negative end of; -A: that of its -A neighbour)
-    const WideLayout W = wide_layout(M, variant);
+    const WideLayout W = wide_layout(M, variant, opt);
     std::vector<int> slot_of((size_t)M.nvox * 3, -1);
     int t = 0;
     for (int a = 0; a < 3; ++a)

@@ -14,10 +14,16 @@ namespace vxh {
 // Wide kernel (kernels_wide.hpp; robots of up to WIDE_BLOCK voxels and 1023 bonds): its bond records share their LDS region with
 // the scratch of the whole-robot passes (12 * BLOCK doubles, then the mesh vertices of a robot in a fluid); the record that stays
 // zero lies behind both.
+// Option wide_small: a wide-listed robot of up to VXH_WIDE_SMALL_VOX voxels that is not under StopConditionType 4-7 and whose LDS, laid out with
+// voxel planes of that many slots and INCLUDING its contact rows, fits the share of a CU's LDS that VXH_WIDE_SMALL_PER_CU workgroups leave
+// each other takes the VXH_WIDE_SMALL_BLOCK-thread instances (wide_small: taken, and then its TABG choice, second pose tile and LDS bytes);
+// its record region follows from the smaller scratch (wide_layout).  Every other robot keeps the 512-thread instances and their layout.
 constexpr int WIDE_BLOCK = 512;
 struct WideLayout { int zidx = 0, region = 0; };
-WideLayout wide_layout(const RobotModel& M, int variant);
+struct WideSmall { int taken = 0, tabg = 0, two_tiles = 0; size_t lds = 0; };
+WideLayout wide_layout(const RobotModel& M, int variant, const Options& opt);
 bool wide_listed(const RobotModel& M, int variant, const Options& opt);
+WideSmall wide_small(const RobotModel& M, int variant, const Options& opt);
 // workgroup size of the resident kernel for a robot of n voxels: its size class
 int resident_block(int n);
 // Resident kernel (kernels_fused.hpp) or wide kernel, one workgroup per robot: the variant follows from the robot's size, fluid, and the

@@ -47,6 +47,13 @@ enum { VXH_RIMG_CAP = 2048 };        // entries of a saved contact-row image (th
 enum { VXH_FUSED_STATIC_LDS = 480 }; // resident kernel (kernels_fused.hpp): upper bound of its static __shared__ variables
 enum { VXH_WIDE_REC = 13,            // wide kernel (kernels_wide.hpp): doubles of a bond record in LDS
        VXH_WIDE_STATIC_LDS = 480 };  // ... and the upper bound of its static __shared__ variables
+// The small instances of the wide kernel (option wide_small): 256 threads for robots of up to 128 voxels (384 bonds), voxel planes of 128
+// slots, LDS sized by the robot so that PER_CU workgroups share a CU (the LDS budget of one: 160 KB / PER_CU, less the static bound) --
+// which is also what __launch_bounds__ promises the registers for (2: 256 VGPRs; 3: 168)
+#ifndef VXH_WIDE_SMALL_RESIDENCY          // (make EXTRA=-DVXH_WIDE_SMALL_RESIDENCY=3: the other residency, for A/B runs)
+#define VXH_WIDE_SMALL_RESIDENCY 2
+#endif
+enum { VXH_WIDE_SMALL_BLOCK = 256, VXH_WIDE_SMALL_VOX = 128, VXH_WIDE_SMALL_PER_CU = VXH_WIDE_SMALL_RESIDENCY, VXH_WIDE_SMALL_STATIC_LDS = 384 };
 
 struct DRobot {               // constant per robot
     int vox_begin, nvox, surf_begin, nsurf, flags, stop_type, excl_wpr;

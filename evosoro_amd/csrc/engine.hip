@@ -403,6 +403,7 @@ const OptionDesc option_table[] = {
     {"tile_small",        &Options::tile_small,        OptionDesc::FLAG, OptionDesc::WHOLE, 0, 1,      true,  false},
     {"wide",              &Options::wide,              OptionDesc::FLAG, OptionDesc::WHOLE, 0, 1,      true,  false},
     {"wide_two_tiles",    &Options::wide_two_tiles,    OptionDesc::FLAG, OptionDesc::WHOLE, 0, 1,      true,  false},
+    {"wide_small",        &Options::wide_small,        OptionDesc::FLAG, OptionDesc::WHOLE, 0, 1,      true,  false},
     {"col_cap",           &Options::col_cap,           OptionDesc::INT,  OptionDesc::RANGE, 0, 1e6,    true,  false},
     {"fused",             &Options::fused,             OptionDesc::FLAG, OptionDesc::WHOLE, 0, 1,      true,  true},
     {"steps_per_launch",  &Options::steps_per_launch,  OptionDesc::INT,  OptionDesc::RANGE, 1, 200000, false, false},
@@ -695,7 +696,7 @@ void Engine::reset() { if (!robots_.empty()) prepare(); }
 static void launch_group(const DBatch& B, int block, bool fluid, bool tabg, bool wide, bool stats, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters, int two_tiles = 0,
                          const unsigned long long* order_in = nullptr, unsigned long long* order_out = nullptr, bool cost = false)
 {
-    if (wide) { launch_wide_group(B, fluid, tabg, stats, list, count, lds, s, cap, iters, two_tiles); return; }
+    if (wide) { launch_wide_group(B, block, fluid, tabg, stats, list, count, lds, s, cap, iters, two_tiles); return; }
     if (fluid) launch_fused_mesh(B, block, tabg, list, count, lds, s, cap, iters, order_in, order_out, cost);
     else launch_fused_land(B, block, tabg, list, count, lds, s, cap, iters, order_in, order_out, cost, stats);
 }

@@ -49,6 +49,7 @@ struct Options {
     int tile_small = 0;                        // also tile large robots the resident kernel could take when the population is small (see tile_candidates(), batch.cpp)
     int wide = 1;                              // small robots (up to 512 voxels, 1023 bonds) go to the wide kernel (kernels_wide.hpp); 0: resident kernel
     int wide_two_tiles = 1;                    // ... with a second pose tile in LDS where it fits (two barriers per step instead of three); 0: cross-checks
+    int wide_small = 0;                        // ... and robots of up to 128 voxels by its 256-thread instances, LDS sized by the robot, several workgroups per CU (opt-in)
     int col_cap = 0;                           // partners a contact row can hold; 0 = every other surface voxel (unbounded, like the reference)
     int fused = 1;                             // one-workgroup-per-robot fused kernel when every robot has <= 1024 voxels
     // fused and tiled paths: time steps per kernel launch.  A launch of a self-colliding population carries ~0.07 ms of fixed cost (0.27 ms until round 3; it

@@ -506,14 +506,16 @@ struct DragCache {
 // tile then takes the facets' contributions -- one chunk of up to SCR_DOUBLES / 3 facets, where the resident kernel needs two for a
 // robot of 8^3 --; a voxel's sum over its facets requests four contributions at a time (same order of additions); the tile is not
 // re-zeroed (the wide kernel's bond records are written, not accumulated).  Same operations per vertex and facet, same sums: same bits.
-template <int BLOCK, int SCR_DOUBLES, bool LEAN = false>
+// PS: the plane stride of what is indexed by voxel (the pose tile, the corner planes of `scr`) where it is not the workgroup's size: the small
+// instances of the wide kernel, more threads than voxel slots.  Vertices and facets are handed out by BLOCK, the threads, as everywhere.
+template <int BLOCK, int SCR_DOUBLES, bool LEAN = false, int PS = BLOCK>
 __device__ __forceinline__ d3 fused_drag(const DBatch& B, const DRobot& R, const double* ps, const double* st, unsigned st_stride, double* sh,
                                          double* scr, bool valid, int v, d3 lm, double mass_inv, const DragCache<BLOCK>& kept,
                                          double* spd_ext = nullptr, int spd_stride = 0)
 {
-    constexpr bool WIDE = SCR_DOUBLES >= 12 * BLOCK;
+    constexpr bool WIDE = SCR_DOUBLES >= 12 * PS;
     constexpr int CPP = WIDE ? 4 : 2;               // voxel corners per pass
-    static_assert(SCR_DOUBLES >= 3 * CPP * BLOCK, "accumulator tile too small for the corner passes");
+    static_assert(SCR_DOUBLES >= 3 * CPP * PS, "accumulator tile too small for the corner passes");
     const double nom = R.lat;
     const int nmv = R.nmv;
     const int tid = threadIdx.x;
@@ -551,8 +553,8 @@ __device__ __forceinline__ d3 fused_drag(const DBatch& B, const DRobot& R, const
         d3 vp = mk3(0, 0, 0), hp = mk3(0, 0, 0), hn = mk3(0, 0, 0);
         RotFwd M;
         if (valid) {
-            vp = mk3(ps[tid], ps[BLOCK + tid], ps[2 * BLOCK + tid]);
-            M = RotFwd(mkq(ps[4 * BLOCK + tid], ps[5 * BLOCK + tid], ps[6 * BLOCK + tid], ps[7 * BLOCK + tid]));
+            vp = mk3(ps[tid], ps[PS + tid], ps[2 * PS + tid]);
+            M = RotFwd(mkq(ps[4 * PS + tid], ps[5 * PS + tid], ps[6 * PS + tid], ps[7 * PS + tid]));
             // CornerPosCur / CornerNegCur (LW/VXS_Voxel.cpp:472-475)
             hp = mk3((1 + st[tid]) * nom * 0.5, (1 + st[st_stride + tid]) * nom * 0.5, (1 + st[2 * st_stride + tid]) * nom * 0.5);
             hn = mk3(-(1 + st[3 * st_stride + tid]) * nom * 0.5, -(1 + st[4 * st_stride + tid]) * nom * 0.5, -(1 + st[5 * st_stride + tid]) * nom * 0.5);
@@ -565,7 +567,7 @@ __device__ __forceinline__ d3 fused_drag(const DBatch& B, const DRobot& R, const
                 for (int c = 0; c < CPP; ++c) {
                     const int corner = p0 + c;
                     const d3 p = vp + M(mk3((corner & 4) ? hp.x : hn.x, (corner & 2) ? hp.y : hn.y, (corner & 1) ? hp.z : hn.z));
-                    scr[(3 * c) * BLOCK + tid] = p.x; scr[(3 * c + 1) * BLOCK + tid] = p.y; scr[(3 * c + 2) * BLOCK + tid] = p.z;
+                    scr[(3 * c) * PS + tid] = p.x; scr[(3 * c + 1) * PS + tid] = p.y; scr[(3 * c + 2) * PS + tid] = p.z;
                 }
             }
             __syncthreads();
@@ -586,7 +588,7 @@ __device__ __forceinline__ d3 fused_drag(const DBatch& B, const DRobot& R, const
                     if (!((vr.w2 >> (20 + corner)) & 1u)) continue;
                     const unsigned word = corner < 3 ? vr.w0 : (corner < 6 ? vr.w1 : vr.w2);
                     const unsigned l = (word >> (10 * (corner % 3))) & 1023u;
-                    part = part + mk3(scr[(3 * c) * BLOCK + l], scr[(3 * c + 1) * BLOCK + l], scr[(3 * c + 2) * BLOCK + l]);
+                    part = part + mk3(scr[(3 * c) * PS + l], scr[(3 * c + 1) * PS + l], scr[(3 * c + 2) * PS + l]);
                 }
                 if (p0 + CPP == 8) {
                     const double inv = vrcp((double)__popc((vr.w2 >> 20) & 255u));

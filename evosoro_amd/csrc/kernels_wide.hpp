@@ -24,6 +24,10 @@
 //   st   [6][BLOCK]   MESH: directional strains
 //   cmask, rc_a1, rc_code   contact rows of colliding robots (rows_to_lds)
 //   ps'  [8][BLOCK]   (two_tiles) second pose tile, at the end: a step's new poses go into the tile nobody reads
+// The small instances (BLOCK = VXH_WIDE_SMALL_BLOCK = 256, option wide_small): robots of up to VXH_WIDE_SMALL_VOX = 128 voxels.
+// 256 threads -- always `split`: translation on wavefronts 0-1, rotation + actuation on 3-2, thread t takes bond entries t and t + 256 -- but
+// every [BLOCK] above is [128] (PS in the kernel) and the scratch is 12 * 128 doubles: the LDS is sized by the robot, not by the block, so that
+// VXH_WIDE_SMALL_PER_CU workgroups share a CU (batch.cpp wide_small) and fill each other's issue gaps.  Same device functions, operands, order.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -91,22 +95,28 @@ __device__ __forceinline__ d3 wide_gather(const double* rec, int g0, int g1, int
 // lane writes the history rings and decides the rule -- in front of one more barrier, because here EVERY thread reads the next step's control
 // words right behind (X).
 template <int BLOCK, bool MESH, bool TABG, bool STATS = false>
-__global__ __launch_bounds__(BLOCK, BLOCK / 256) void k_robot_wide(DBatch B, const DRobot* __restrict__ robots,
+__global__ __launch_bounds__(BLOCK, BLOCK == VXH_WIDE_SMALL_BLOCK ? VXH_WIDE_SMALL_PER_CU : BLOCK / 256) void k_robot_wide(DBatch B, const DRobot* __restrict__ robots,
                                                                    const int* __restrict__ robot_list, long long step_cap, int iters,
                                                                    int lds_doubles_given, int two_tiles)
 {
     extern __shared__ __align__(16) double lds[];
     static_assert(!(STATS && MESH), "STATS instances: _voxcad robots");
+    // PS: the plane stride of everything indexed by voxel (pose tile, strains, contact masks) and the unit of the scratch.  The workgroup's
+    // size -- except in the small instances (BLOCK = VXH_WIDE_SMALL_BLOCK: robots of up to VXH_WIDE_SMALL_VOX voxels, always `split`,
+    // their LDS sized by the robot so that several workgroups share a CU), where threads beyond PS never own a voxel-indexed slot.
+    constexpr bool SMALL = BLOCK == VXH_WIDE_SMALL_BLOCK;
+    constexpr int PS = SMALL ? (int)VXH_WIDE_SMALL_VOX : BLOCK;
+    static_assert(!(SMALL && STATS), "no STATS instances of the small block");
     const int lds_doubles_all = lds_doubles_given - (STATS ? (int)VXH_STAT_LDS : 0);
     double* const sst = lds + lds_doubles_all;     // STATS: [3][16] per wavefront kinetic energy, strain energy, max |v|^2 of the step
     // two_tiles: a second pose tile at the end of the dynamic LDS (the host grants it where the robot's layout leaves 8 * BLOCK
     // doubles: every walker, the smaller swimmers).  The new poses then go into the OTHER tile during the voxel phase -- nobody reads
     // it -- and the step has two workgroup barriers instead of three (see the step loop).
-    const int lds_doubles = lds_doubles_all - (two_tiles ? 8 * BLOCK : 0);
+    const int lds_doubles = lds_doubles_all - (two_tiles ? 8 * PS : 0);
     double* const ps_a = lds;
     double* const ps_b = two_tiles ? lds + lds_doubles : lds;
     double* ps = ps_a;                        // the tile that holds the poses at the start of the step
-    double* const rec = lds + 8 * BLOCK;
+    double* const rec = lds + 8 * PS;
     __shared__ DRobotState rs;
     __shared__ FusedCtl s_ctl[2];
     // ping-pong control words of the step loop (slot = step parity): a bond diverged in this step; max |v|^2 of this step's voxel
@@ -116,6 +126,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void k_robot_wide(DBatch B, con
     __shared__ double s_disp[2];
     __shared__ int s_seg[2 * (BLOCK / 64)];
     static_assert(sizeof(DRobotState) + 2 * sizeof(FusedCtl) + 2 * sizeof(int) + 4 * sizeof(double) + 2 * 16 * sizeof(int) + 16 <= VXH_WIDE_STATIC_LDS, "static LDS bound");
+    static_assert(!SMALL || sizeof(DRobotState) + 2 * sizeof(FusedCtl) + 2 * sizeof(int) + 4 * sizeof(double) + sizeof(s_seg) + 16 <= VXH_WIDE_SMALL_STATIC_LDS, "static LDS bound of the small block");
 
     const int tid = threadIdx.x;
     const int r = __builtin_amdgcn_readfirstlane(robot_list[blockIdx.x]);
@@ -148,16 +159,16 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void k_robot_wide(DBatch B, con
         bct = (const DBondClass*)tabs;
         vct = (const DVoxClass*)(tabs + nbd);
     }
-    double* const st = tabs + nbd + nvd;                       // MESH: [6][BLOCK]
+    double* const st = tabs + nbd + nvd;                       // MESH: [6][PS]
     const int nvs = (nvox + 63) & ~63;
-    double* const mesh = rec + 12 * BLOCK + 3 * nvs;           // a robot in a fluid: the voxels' velocities [3][nvs] and the mesh vertices, inside the record region, behind the scratch
-    unsigned long long* const cmask = (unsigned long long*)(st + (MESH ? 6 * BLOCK : 0));
-    double* const rc_a1 = (double*)cmask + BLOCK;
+    double* const mesh = rec + 12 * PS + 3 * nvs;           // a robot in a fluid: the voxels' velocities [3][nvs] and the mesh vertices, inside the record region, behind the scratch
+    unsigned long long* const cmask = (unsigned long long*)(st + (MESH ? 6 * PS : 0));
+    double* const rc_a1 = (double*)cmask + PS;
     const int pool_cap = (R.flags & RF_SELF_COL) ? max(0, (int)((lds_doubles - (int)(rc_a1 - lds)) * 2 / 3) - 1) : 0;
     int* const rc_code = (int*)(rc_a1 + pool_cap);
     if constexpr (MESH) {
 #pragma unroll
-        for (int k = 0; k < 6; ++k) st[k * BLOCK + tid] = valid ? B.strain[(unsigned)k * nv + (unsigned)v] : 0.0;
+        for (int k = 0; k < 6; ++k) if (!SMALL || tid < PS) st[k * PS + tid] = valid ? B.strain[(unsigned)k * nv + (unsigned)v] : 0.0;
     }
     for (int k = tid; k < VXH_WIDE_REC; k += BLOCK) rec[R.wzidx * VXH_WIDE_REC + k] = 0.0;     // the zero record
     __syncthreads();
@@ -179,14 +190,14 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void k_robot_wide(DBatch B, con
         if (valid) {
             gl0 = B.wgather[v]; gl1 = B.wgather[nv + v];
             lm = mk3(LINMOM(0, v), LINMOM(1, v), LINMOM(2, v));
-            ps[tid] = POS(b0, 0, v); ps[BLOCK + tid] = POS(b0, 1, v); ps[2 * BLOCK + tid] = POS(b0, 2, v);
+            ps[tid] = POS(b0, 0, v); ps[PS + tid] = POS(b0, 1, v); ps[2 * PS + tid] = POS(b0, 2, v);
         }
         if (angr) {
             ga0 = B.wgather[va]; ga1 = B.wgather[nv + va];
             amp_damp = B.amp_damp[va]; ph_sin = B.act_sb[va]; ph_cos = B.act_cb[va];
             am = mk3(ANGMOM(0, va), ANGMOM(1, va), ANGMOM(2, va));
-            ps[3 * BLOCK + la] = SCALE(b0, va);
-            ps[4 * BLOCK + la] = QUAT(0, va); ps[5 * BLOCK + la] = QUAT(1, va); ps[6 * BLOCK + la] = QUAT(2, va); ps[7 * BLOCK + la] = QUAT(3, va);
+            ps[3 * PS + la] = SCALE(b0, va);
+            ps[4 * PS + la] = QUAT(0, va); ps[5 * PS + la] = QUAT(1, va); ps[6 * PS + la] = QUAT(2, va); ps[7 * PS + la] = QUAT(3, va);
         }
     }
     DragCache<BLOCK> dcache;
@@ -200,7 +211,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void k_robot_wide(DBatch B, con
         int row = -1;
         if (valid) { const int so = B.surf_ord[v]; if (so >= 0) row = R.surf_begin + so; }
         const int ccnt = row >= 0 ? B.col_cnt[row] : 0;
-        if (pool_cap > 0) cmask[tid_r] = 0;
+        if (pool_cap > 0 && (!SMALL || tid_r < PS)) cmask[tid_r] = 0;
         __syncthreads();
         const int ccnt_l = ccnt <= 64 ? ccnt : 0;     // (a longer row stays in memory: 64 mask bits per voxel)
         int incl = ccnt_l;
@@ -263,7 +274,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void k_robot_wide(DBatch B, con
         const FusedCtl& K = s_ctl[par];
         FusedCtl& Knext = s_ctl[par ^ 1];
         double* const psn = ps == ps_a ? ps_b : ps_a;      // where the new poses go (the same tile without the second one)
-        const FetchLds<BLOCK> fetch{ps, base};
+        const FetchLds<PS> fetch{ps, base};
         const int kf = __builtin_amdgcn_readfirstlane(K.flags);
         const bool k_go = kf & 1, k_latch = kf & 2, k_eol = kf & 4, k_rebuild = (kf & 8) || reb_next, k_trace = kf & VXH_CTL_TRACE_BITS;
         if (!k_go && !k_trace) break;
@@ -271,18 +282,18 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void k_robot_wide(DBatch B, con
         asm volatile("" : "+v"(vv));
         asm volatile("" : "+v"(vva));
         if (k_latch || k_eol || k_trace)
-            fused_latch_cm<BLOCK>(B, R, rs, ps, rec, valid, Cl, k_latch, k_eol, fused_trace_mask(kf), K.trace_index);
+            fused_latch_cm<PS>(B, R, rs, ps, rec, valid, Cl, k_latch, k_eol, fused_trace_mask(kf), K.trace_index);
         if (!k_go) break;
         StatSamples smp;                       // STATS, control lane: the older sampled entries of the rule's history, requested now, read behind (X)
         if constexpr (STATS) { if (ctl_thread) smp = stat_prefetch(Q, R, sslot, rs.steps + 1); }
         if (__builtin_expect(k_rebuild, 0)) {
-            fused_rebuild<BLOCK>(B, R, rs, ps, rec, 12 * BLOCK, (double*)cmask, max(0, lds_doubles - (int)((double*)cmask - lds)), vct);
+            fused_rebuild<PS>(B, R, rs, ps, rec, 12 * PS, (double*)cmask, max(0, lds_doubles - (int)((double*)cmask - lds)), vct);
             rows_to_lds();
             if (reach_early) npairs = pairs_in_copy();
         }
         d3 drag = mk3(0, 0, 0);
         const bool fluid = MESH && (R.flags & RF_FLUID) != 0;
-        if constexpr (MESH) { if (fluid) drag = fused_drag<BLOCK, 12 * BLOCK, true>(B, R, ps, st, (unsigned)BLOCK, mesh, rec, valid, vv, lm, Cl.mass_inv, dcache, rec + 12 * BLOCK, nvs); }
+        if constexpr (MESH) { if (fluid) drag = fused_drag<BLOCK, 12 * PS, true, PS>(B, R, ps, st, (unsigned)PS, mesh, rec, valid, vv, lm, Cl.mass_inv, dcache, rec + 12 * PS, nvs); }
         const bool damp_on = (kf & 32) != 0;
         VXH_T_MARK(1)
 
@@ -290,13 +301,13 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void k_robot_wide(DBatch B, con
         bool div = false;
         double bond_e = 0;                     // STATS: strain energy of this lane's bonds
         if constexpr (STATS) {
-            if (e0 != -1) div = wide_bond<BLOCK, MESH, true>(B, R, bct, ps, rec, e0, tid, modebits, 0, damp_on, st, &bond_e, Q.bond_energy);
-            if (e1 != -1) div = wide_bond<BLOCK, MESH, true>(B, R, bct, ps, rec, e1, tid + BLOCK, modebits, 2, damp_on, st, &bond_e, Q.bond_energy) || div;
+            if (e0 != -1) div = wide_bond<PS, MESH, true>(B, R, bct, ps, rec, e0, tid, modebits, 0, damp_on, st, &bond_e, Q.bond_energy);
+            if (e1 != -1) div = wide_bond<PS, MESH, true>(B, R, bct, ps, rec, e1, tid + BLOCK, modebits, 2, damp_on, st, &bond_e, Q.bond_energy) || div;
         } else {
-            if (e0 != -1) div = wide_bond<BLOCK, MESH>(B, R, bct, ps, rec, e0, tid, modebits, 0, damp_on, st);
-            if (e1 != -1) div = wide_bond<BLOCK, MESH>(B, R, bct, ps, rec, e1, tid + BLOCK, modebits, 2, damp_on, st) || div;
+            if (e0 != -1) div = wide_bond<PS, MESH>(B, R, bct, ps, rec, e0, tid, modebits, 0, damp_on, st);
+            if (e1 != -1) div = wide_bond<PS, MESH>(B, R, bct, ps, rec, e1, tid + BLOCK, modebits, 2, damp_on, st) || div;
         }
-        if (reach_early && wave >= nbw) fused_contact_reach_all<BLOCK>(ps, 0, npairs, wave - nbw, NWAVES - nbw, cmask, rc_code);
+        if (reach_early && wave >= nbw) fused_contact_reach_all<PS>(ps, 0, npairs, wave - nbw, NWAVES - nbw, cmask, rc_code);
         if (div) s_divf[par] = 1;
         VXH_T_MARK(2)
         __syncthreads();                       // (B)
@@ -316,14 +327,14 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void k_robot_wide(DBatch B, con
         d3 pos = mk3(0, 0, 0);
         if ((R.flags & RF_SELF_COL) && !reach_early) {
             const int nseg = s_seg[2 * (tid >> 6) + 1];
-            if (nseg > 0) fused_contact_reach<BLOCK>(ps, s_seg[2 * (tid >> 6)], nseg, cmask, rc_code);
+            if (nseg > 0) fused_contact_reach<PS>(ps, s_seg[2 * (tid >> 6)], nseg, cmask, rc_code);
         }
         if (valid) {
             const d3 vel = lm * Cl.mass_inv;
             d3 F = wide_gather(rec, gl0, gl1, 0, (vel * (-R.slow_z)) * Cl.c_lin);
-            pos = mk3(ps[tid], ps[BLOCK + tid], ps[2 * BLOCK + tid]);
-            const double scale = ps[3 * BLOCK + tid];
-            if (rowd != 0) F = fused_contact_forces<BLOCK>(B, R, ps, F, pos, scale, tid, vv, rowd, cmask, rc_code, rc_a1);
+            pos = mk3(ps[tid], ps[PS + tid], ps[2 * PS + tid]);
+            const double scale = ps[3 * PS + tid];
+            if (rowd != 0) F = fused_contact_forces<PS>(B, R, ps, F, pos, scale, tid, vv, rowd, cmask, rc_code, rc_a1);
             vel2 = voxel_update_lin(B, R, Cl, vv, fetch, F, vel, pos, lm, scale, -1, 0, fluid, drag);
         }
         // ---- voxel phase, rotation and size
@@ -331,8 +342,8 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void k_robot_wide(DBatch B, con
         double scale_a = 0;
         if (angr) {
             const d3 M = wide_gather(rec, ga0, ga1, 3, mk3(0, 0, 0));
-            scale_a = ps[3 * BLOCK + la];
-            ang = mkq(ps[4 * BLOCK + la], ps[5 * BLOCK + la], ps[6 * BLOCK + la], ps[7 * BLOCK + la]);
+            scale_a = ps[3 * PS + la];
+            ang = mkq(ps[4 * PS + la], ps[5 * PS + la], ps[6 * PS + la], ps[7 * PS + la]);
             voxel_update_ang(B, R, Ca, vva, K.time, K.act_sin, K.act_cos, K.prenatal_c, M, am, ang, scale_a, ph_sin, ph_cos, amp_damp);
         }
         if constexpr (STATS) {                  // the wavefront's share of TotalObjKineticE, TotalObjStrainE and MaxVoxVel^2 (every lane takes part)
@@ -346,10 +357,10 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void k_robot_wide(DBatch B, con
             if ((tid & 63) == 0) atomicMax(&s_mv[par], (unsigned long long)__double_as_longlong(vel2));
         }
         auto store_poses = [&]() {
-            if (valid) { psn[tid] = pos.x; psn[BLOCK + tid] = pos.y; psn[2 * BLOCK + tid] = pos.z; }
+            if (valid) { psn[tid] = pos.x; psn[PS + tid] = pos.y; psn[2 * PS + tid] = pos.z; }
             if (angr) {
-                psn[3 * BLOCK + la] = scale_a;
-                psn[4 * BLOCK + la] = ang.w; psn[5 * BLOCK + la] = ang.x; psn[6 * BLOCK + la] = ang.y; psn[7 * BLOCK + la] = ang.z;
+                psn[3 * PS + la] = scale_a;
+                psn[4 * PS + la] = ang.w; psn[5 * PS + la] = ang.x; psn[6 * PS + la] = ang.y; psn[7 * PS + la] = ang.z;
             }
         };
         if (two_tiles) store_poses();          // (into the tile nobody reads)
@@ -399,19 +410,19 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void k_robot_wide(DBatch B, con
     {
         const int b1 = rs.steps & 1;
         if (valid) {
-            POS(b1, 0, v) = ps[tid]; POS(b1, 1, v) = ps[BLOCK + tid]; POS(b1, 2, v) = ps[2 * BLOCK + tid];
+            POS(b1, 0, v) = ps[tid]; POS(b1, 1, v) = ps[PS + tid]; POS(b1, 2, v) = ps[2 * PS + tid];
             LINMOM(0, v) = lm.x; LINMOM(1, v) = lm.y; LINMOM(2, v) = lm.z;
         }
         if (angr) {
-            SCALE(b1, va) = ps[3 * BLOCK + la];
-            QUAT(0, va) = ps[4 * BLOCK + la]; QUAT(1, va) = ps[5 * BLOCK + la]; QUAT(2, va) = ps[6 * BLOCK + la]; QUAT(3, va) = ps[7 * BLOCK + la];
+            SCALE(b1, va) = ps[3 * PS + la];
+            QUAT(0, va) = ps[4 * PS + la]; QUAT(1, va) = ps[5 * PS + la]; QUAT(2, va) = ps[6 * PS + la]; QUAT(3, va) = ps[7 * PS + la];
             ANGMOM(0, va) = am.x; ANGMOM(1, va) = am.y; ANGMOM(2, va) = am.z;
         }
     }
     if constexpr (MESH) {
         if (valid) {
 #pragma unroll
-            for (int k = 0; k < 6; ++k) B.strain[(unsigned)k * nv + (unsigned)v] = st[k * BLOCK + tid];
+            for (int k = 0; k < 6; ++k) B.strain[(unsigned)k * nv + (unsigned)v] = st[k * PS + tid];
         }
     }
     if (e0 != -1) B.small_angle[(unsigned)((e0 >> 18) & 3) * nv + (base + (e0 & 511))] = (unsigned char)(modebits & 3u);

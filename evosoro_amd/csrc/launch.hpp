@@ -36,9 +36,9 @@ void launch_fused_land(const DBatch& B, int block, bool tabg, const int* list, i
                        const unsigned long long* order_in, unsigned long long* order_out, bool cost, bool stats = false);
 void launch_fused_mesh(const DBatch& B, int block, bool tabg, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters,
                        const unsigned long long* order_in, unsigned long long* order_out, bool cost);
-// k_robot_wide<512, MESH, TABG, STATS> (kernels_wide.hpp); stats (with launch_fused_land too): the STATS instances, for groups of robots under
-// StopConditionType 4-7
-void launch_wide_group(const DBatch& B, bool mesh, bool tabg, bool stats, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters, int two_tiles);
+// k_robot_wide<block, MESH, TABG, STATS> (kernels_wide.hpp); block: 512, or VXH_WIDE_SMALL_BLOCK for a group of small robots (option wide_small);
+// stats (with launch_fused_land too): the STATS instances, for groups of robots under StopConditionType 4-7 (512 only)
+void launch_wide_group(const DBatch& B, int block, bool mesh, bool tabg, bool stats, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters, int two_tiles);
 // k_tile_steps<TABG, MESH, FLUID> (kernels_tiled.hpp); mesh_kind: 0 = _voxcad, 1 = land_water robot on land, 2 = in a fluid
 // small: every tile of the launch within VXH_TILE_S_OWN / _HALO / _BONDS (device_types.hpp): the instances with compile-time LDS strides
 void launch_tile_group(const DBatch& B, bool tabg, int mesh_kind, bool small, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters, unsigned gen);

@@ -240,6 +240,11 @@ int  vxh_count_bond_modes(const vxh_engine* e, long long* large_angle_out, long 
  *                       rounds (cross-checks).  Like "tiled" a function of the robot alone.
  *   "wide_two_tiles"    1 (default) = the wide kernel keeps a second pose tile in LDS where the robot's layout leaves room for it and
  *                       steps with two workgroup barriers instead of three; 0 = one tile (cross-checks).  Same arithmetic, same bits.
+ *   "wide_small"        1 = wide-listed robots of up to 128 voxels (384 bonds) that are not under StopConditionType 4-7 are stepped by the
+ *                       256-thread instances of the wide kernel, whose LDS is sized by the robot -- contact rows included: with "col_cap"
+ *                       set, rows of that length; else a pool of 8 KB -- so that two workgroups share a CU; a robot whose layout passes
+ *                       that share keeps the 512-thread instances.  Same device functions on the same operands in the same order: the
+ *                       state bytes are those of 0.  Default 0: opt-in until the parity ledger has been run with it.
  *   "col_cap"           partners a collision row can hold.  0 (default) = every other surface voxel of the robot, i.e. unbounded like
  *                       the reference's lists (CVX_Sim::CreateColBond has no cap); memory: 12-16 bytes x nsurf^2 per colliding robot
  *                       (5 MB for a 10x10x10 robot), touched only as far as rows really grow.  n > 0 bounds the rows at n partners

@@ -664,10 +664,24 @@ void tile_mesh_counts(const RobotModel& M, int variant, const TilePlan::Tile& t,
         }
 }
 
-struct Planned { int r; TilePlan plan; int tabg; size_t lds; int mesh; int small; };
+struct Planned { int r; TilePlan plan; int tabg; size_t lds; int mesh; int cls; };
 
-// one robot, starting from k tiles: more of them until every tile fits the workgroup and its LDS; false: cannot be tiled, left to the other kernels
-bool plan_robot_tiles(const RobotModel& M, int r, int variant, int k, Planned& out)
+// the size class of a robot's tiles, a function of the tiles alone: SMALL when every tile is within VXH_TILE_S_*, else MEDIUM when every tile is
+// within VXH_TILE_M_*, else GENERIC
+int tile_size_class(const TilePlan& P)
+{
+    bool small = true, medium = true;
+    for (const auto& t : P.tiles) {
+        const int own = (int)t.own.size(), halo = (int)t.halo.size(), nb = (int)t.bond_v1.size();
+        small = small && own <= VXH_TILE_S_OWN && halo <= VXH_TILE_S_HALO && nb <= VXH_TILE_S_BONDS;
+        medium = medium && own <= VXH_TILE_M_OWN && halo <= VXH_TILE_M_HALO && nb <= VXH_TILE_M_BONDS;
+    }
+    return small ? VXH_TILE_CLASS_SMALL : medium ? VXH_TILE_CLASS_MEDIUM : VXH_TILE_CLASS_GENERIC;
+}
+
+// one robot, starting from k tiles: more of them until every tile fits the workgroup and its LDS; false: cannot be tiled, left to the other kernels.
+// tile_medium (the engine option): MEDIUM robots take that class's instances and its fixed layout; without it they stay GENERIC
+bool plan_robot_tiles(const RobotModel& M, int r, int variant, int k, bool tile_medium, Planned& out)
 {
     const size_t lds_cap = 160 * 1024 - VXH_TILE_STATIC_LDS;
     const int tab_doubles = (int)(M.bond_classes.size() * sizeof(DBondClass) / 8 + M.vox_classes.size() * sizeof(DVoxClass) / 8);
@@ -675,18 +689,26 @@ bool plan_robot_tiles(const RobotModel& M, int r, int variant, int k, Planned& o
     k = std::max(1, std::min(k, M.nvox / 8));
     for (;;) {
         TilePlan P = plan_tiles(M, k);
-        size_t lds = 0;
-        bool small = true;                                    // every tile within the SMALL size class: its kernel instances, its (fixed) layout
-        for (const auto& t : P.tiles) small = small && (int)t.own.size() <= VXH_TILE_S_OWN && (int)t.halo.size() <= VXH_TILE_S_HALO && (int)t.bond_v1.size() <= VXH_TILE_S_BONDS;
-        for (const auto& t : P.tiles) {
-            int n_mv = 0, n_f = 0, n_mx = 0;
-            tile_mesh_counts(M, variant, t, n_mv, n_f, n_mx);
-            const TileLayout TL = small ? tile_layout(VXH_TILE_S_OWN, VXH_TILE_S_HALO, VXH_TILE_S_BONDS, tabg ? 0 : tab_doubles, M.nmv > 0, n_mv, n_f, n_mx)
-                                        : tile_layout((int)t.own.size(), (int)t.halo.size(), (int)t.bond_v1.size(), tabg ? 0 : tab_doubles, M.nmv > 0, n_mv, n_f, n_mx);
-            lds = std::max(lds, (size_t)TL.total * 8);
-        }
+        int cls = tile_size_class(P);                         // every tile within a size class: its kernel instances, its (fixed) layout
+        if (cls == VXH_TILE_CLASS_MEDIUM && !tile_medium) cls = VXH_TILE_CLASS_GENERIC;
+        auto lds_of = [&](int c) {
+            size_t most = 0;
+            for (const auto& t : P.tiles) {
+                int n_mv = 0, n_f = 0, n_mx = 0;
+                tile_mesh_counts(M, variant, t, n_mv, n_f, n_mx);
+                const TileLayout TL = c == VXH_TILE_CLASS_SMALL ? tile_layout(VXH_TILE_S_OWN, VXH_TILE_S_HALO, VXH_TILE_S_BONDS, tabg ? 0 : tab_doubles, M.nmv > 0, n_mv, n_f, n_mx)
+                                    : c == VXH_TILE_CLASS_MEDIUM ? tile_layout(VXH_TILE_M_OWN, VXH_TILE_M_HALO, VXH_TILE_M_BONDS, tabg ? 0 : tab_doubles, M.nmv > 0, n_mv, n_f, n_mx)
+                                            : tile_layout((int)t.own.size(), (int)t.halo.size(), (int)t.bond_v1.size(), tabg ? 0 : tab_doubles, M.nmv > 0, n_mv, n_f, n_mx);
+                most = std::max(most, (size_t)TL.total * 8);
+            }
+            return most;
+        };
+        size_t lds = lds_of(cls);
+        // (a fluid tile's mesh arrays behind the MEDIUM layout can exceed the LDS where the tile's own layout fits: the robot then keeps the
+        // tiles it has with the option off, and the GENERIC instances)
+        if (cls == VXH_TILE_CLASS_MEDIUM && lds > lds_cap) { cls = VXH_TILE_CLASS_GENERIC; lds = lds_of(cls); }
         if (P.k > VXH_TILE_MAX_TILES) return false;           // (left to the other kernels)
-        if (P.max_own <= VXH_TILE_BLOCK && P.max_local <= 1024 && lds <= lds_cap) { out = Planned{r, std::move(P), tabg, lds, M.nmv > 0 ? (in_fluid(M, variant) ? 2 : 1) : 0, small ? 1 : 0}; return true; }
+        if (P.max_own <= VXH_TILE_BLOCK && P.max_local <= 1024 && lds <= lds_cap) { out = Planned{r, std::move(P), tabg, lds, M.nmv > 0 ? (in_fluid(M, variant) ? 2 : 1) : 0, cls}; return true; }
         if (k >= M.nvox / 8) return false;                    // cannot be tiled: left to the other kernels
         k = std::min(std::max(k + 1, k * 5 / 4 + 1), std::max(1, M.nvox / 8));
     }
@@ -713,7 +735,7 @@ std::vector<Planned> plan_candidates(const std::vector<RobotModel>& robots, cons
         const int k = opt.tiles_per_robot > 0 ? opt.tiles_per_robot
                                               : (sum_lat <= n_cu ? k_latency(M) : std::max(1, (int)(k_latency(M) * (long long)n_cu / sum_lat)));
         Planned q;
-        if (plan_robot_tiles(M, r, variant, k, q)) planned.push_back(std::move(q));
+        if (plan_robot_tiles(M, r, variant, k, opt.tile_medium != 0, q)) planned.push_back(std::move(q));
     }
     return planned;
 }
@@ -823,15 +845,15 @@ void pack_tile_launches(const std::vector<RobotModel>& robots, const HostBatch& 
                         FluidTileTables& F, LaunchPlan& P)
 {
     const long long capacity = n_cu;
-    for (int kind = 0; kind < 12; ++kind) {
-        const int tabg = kind & 1, mesh = (kind >> 1) % 3, small = kind / 6;      // mesh: 0 _voxcad, 1 land_water on land, 2 land_water in a fluid
+    for (int kind = 0; kind < 18; ++kind) {
+        const int tabg = kind & 1, mesh = (kind >> 1) % 3, cls = kind / 6;      // mesh: 0 _voxcad, 1 land_water on land, 2 land_water in a fluid; cls: VXH_TILE_CLASS_*
         TileLaunchPlan cur;
-        cur.tabg = tabg; cur.mesh = mesh; cur.small = small;
+        cur.tabg = tabg; cur.mesh = mesh; cur.cls = cls;
         for (const auto& q : planned) {
-            if (q.tabg != tabg || q.mesh != mesh || q.small != small) continue;
+            if (q.tabg != tabg || q.mesh != mesh || q.cls != cls) continue;
             const int k = q.plan.k;
             if (k > capacity) continue;                    // more tiles than the chip holds: not tiled
-            if (cur.count > 0 && cur.count + k > capacity) { P.tile_launches.push_back(cur); cur = TileLaunchPlan(); cur.tabg = tabg; cur.mesh = mesh; cur.small = small; }
+            if (cur.count > 0 && cur.count + k > capacity) { P.tile_launches.push_back(cur); cur = TileLaunchPlan(); cur.tabg = tabg; cur.mesh = mesh; cur.cls = cls; }
             cur.lds = std::max(cur.lds, q.lds);
             append_robot_tiles(robots[q.r], q, H, variant, cur, F, P);
         }
@@ -842,8 +864,8 @@ void pack_tile_launches(const std::vector<RobotModel>& robots, const HostBatch& 
         // speed, and the whole robot waits for them at every barrier; asking for more than half of the LDS keeps them apart.
         if (L.count <= n_cu) L.lds = std::max(L.lds, (size_t)(81 * 1024));
         if (std::getenv("VXH_PROF_TILES"))
-            std::fprintf(stderr, "vxhip: tile launch kind tabg=%d mesh=%d: %d tiles of %zu robots, %zu B of LDS, 1 workgroups per CU\n", L.tabg, L.mesh, L.count,
-                         L.robots.size(), L.lds);
+            std::fprintf(stderr, "vxhip: tile launch kind tabg=%d mesh=%d class=%s: %d tiles of %zu robots, %zu B of LDS, 1 workgroups per CU\n", L.tabg, L.mesh,
+                         L.cls == VXH_TILE_CLASS_SMALL ? "SMALL" : L.cls == VXH_TILE_CLASS_MEDIUM ? "MEDIUM" : "GENERIC", L.count, L.robots.size(), L.lds);
     }
 }
 

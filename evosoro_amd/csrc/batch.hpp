@@ -126,7 +126,8 @@ struct GroupPlan {
 // A launch of the tiled kernel: all tiles of its robots, no more than the chip keeps resident
 struct TileLaunchPlan {
     int tabg = 0, mesh = 0, count = 0;   // template arguments of k_tile_steps (mesh: land_water robots, whose strains are part of the state)
-    int small = 0;                    // ... and SMALL: every tile of the launch within VXH_TILE_S_* (compile-time LDS strides)
+    int cls = 0;                      // ... and its size class, VXH_TILE_CLASS_*: SMALL / MEDIUM = every tile of the launch within VXH_TILE_S_* /
+                                      // VXH_TILE_M_* (compile-time LDS strides; MEDIUM only with the option tile_medium)
     size_t lds = 0;
     std::vector<int> tile_ids, robots;
 };

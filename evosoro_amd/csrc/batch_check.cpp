@@ -4,6 +4,8 @@
 //                                                  is then unpacked and compared with the robots' models
 //   batch_check --arrays <variant 0|1> robot.vxa... every file's lattice and layers handed over as arrays (models_from_arrays) must give the
 //                                                  batch the file gives, value for value; and what that route must refuse
+//   batch_check --medium <variant> <CUs> <tiles per robot> <tile_small> robot.vxa...
+//                                                  the size classes of the tiled kernel with the option tile_medium on and off (check_medium)
 //   batch_check --dominant                         dominant_kernel on a table of hand-made calls, one per branch of its rule
 #include <algorithm>
 #include <cstdarg>
@@ -246,6 +248,55 @@ void check_batch(const Robots& robots, int variant, int n_cu, const char* name, 
                 name, nr, H.nv, P.groups.size(), P.tile_launches.size(), n_tiled, P.tiles.size(), P.n_rest);
 }
 
+// ---- --medium: the MEDIUM size class of the tiled kernel (option tile_medium) ----
+// The batch planned with the option on and off: the same tiles either way; per robot the class its tiles' counts give by the rule (SMALL when all
+// are within VXH_TILE_S_*, else MEDIUM when all are within VXH_TILE_M_*, else GENERIC) is its launch's -- MEDIUM only with the option on; the
+// fixed layout of a MEDIUM launch holds every one of its tiles, and no launch asks for more LDS than a CU has.  One line per robot: the ranges
+// of its tiles' own / halo / bond counts and the class.
+void check_medium(const Robots& robots, int variant, int n_cu, int tiles_per_robot, int tile_small)
+{
+    g_set = "tile_medium";
+    Options o;
+    o.tiled = tile_small ? 1 : 2; o.tiles_per_robot = tiles_per_robot; o.tile_small = tile_small;
+    const HostBatch H = assemble_batch(robots, variant, o, 0);
+    const LaunchPlan off = plan_launches(robots, H, variant, o, true, n_cu);
+    o.tile_medium = 1;
+    const LaunchPlan on = plan_launches(robots, H, variant, o, true, n_cu);
+    check_partition(robots, on, n_cu);
+    CHECK(on.tiles.size() == off.tiles.size() && on.robot_tiles == off.robot_tiles && on.tile_bond.size() == off.tile_bond.size(), "the option changed the tiles");
+    const size_t lds_cap = (size_t)160 * 1024 - VXH_TILE_STATIC_LDS;
+    for (const TileLaunchPlan& L : off.tile_launches) CHECK(L.cls != VXH_TILE_CLASS_MEDIUM && L.lds <= lds_cap, "option off: a launch of class %d, %zu B of LDS", L.cls, L.lds);
+    const char* names[3] = {"GENERIC", "SMALL", "MEDIUM"};
+    for (const TileLaunchPlan& L : on.tile_launches) {
+        CHECK(L.cls >= 0 && L.cls <= 2 && L.lds <= lds_cap, "a launch of class %d, %zu B of LDS (cap %zu)", L.cls, L.lds, lds_cap);
+        size_t at = 0;
+        for (int r : L.robots) {
+            int own[2] = {1 << 30, 0}, halo[2] = {1 << 30, 0}, nb[2] = {1 << 30, 0};
+            const RobotModel& M = robots[r];
+            int tabd = (int)(M.bond_classes.size() * sizeof(DBondClass) / 8 + M.vox_classes.size() * sizeof(DVoxClass) / 8);
+            if ((size_t)tabd * 8 > 32 * 1024) tabd = 0;      // (tables left in memory: the TABG instances)
+            bool medium_fits = true;
+            const int k = on.robot_tiles[r];
+            for (int t = 0; t < k; ++t, ++at) {
+                const DTile& d = on.tiles[L.tile_ids[at]];
+                own[0] = std::min(own[0], d.n_own); own[1] = std::max(own[1], d.n_own); halo[0] = std::min(halo[0], d.n_halo); halo[1] = std::max(halo[1], d.n_halo);
+                nb[0] = std::min(nb[0], d.nb); nb[1] = std::max(nb[1], d.nb);
+                const TileLayout TL = tile_layout(VXH_TILE_M_OWN, VXH_TILE_M_HALO, VXH_TILE_M_BONDS, tabd, M.nmv > 0, d.n_mv, d.n_f, d.n_mx);
+                medium_fits = medium_fits && (size_t)TL.total * 8 <= lds_cap;
+                if (L.cls != VXH_TILE_CLASS_MEDIUM) continue;
+                CHECK(d.n_own <= TL.no && d.n_own + d.n_halo <= TL.np && d.nb <= TL.nbp && d.n_halo <= VXH_TILE_BLOCK && d.n_own <= 128, "robot %d: the MEDIUM layout (%d / %d / %d) does not hold a tile of %d / %d / %d", r, TL.no, TL.np, TL.nbp, d.n_own, d.n_halo, d.nb);
+                CHECK((size_t)TL.total * 8 <= L.lds, "robot %d: a tile's MEDIUM layout needs %zu B, the launch asks for %zu", r, (size_t)TL.total * 8, L.lds);
+            }
+            const bool small = own[1] <= VXH_TILE_S_OWN && halo[1] <= VXH_TILE_S_HALO && nb[1] <= VXH_TILE_S_BONDS;
+            const bool medium = own[1] <= VXH_TILE_M_OWN && halo[1] <= VXH_TILE_M_HALO && nb[1] <= VXH_TILE_M_BONDS;
+            const int want = small ? VXH_TILE_CLASS_SMALL : medium && medium_fits ? VXH_TILE_CLASS_MEDIUM : VXH_TILE_CLASS_GENERIC;
+            CHECK(L.cls == want, "robot %d: tiles of up to %d / %d / %d are in a %s launch, expected %s", r, own[1], halo[1], nb[1], names[L.cls], names[want]);
+            std::printf("batch_check --medium: robot %d (%d voxels): %d tiles, own %d-%d, halo %d-%d, bonds %d-%d: %s, %zu B of LDS: ok\n", r, robots[r].nvox, k, own[0], own[1], halo[0], halo[1],
+                        nb[0], nb[1], names[L.cls], L.lds);
+        }
+    }
+}
+
 // ---- --arrays: the in-memory route (models_from_arrays, what vxh_add_robots takes) against the file route ----
 struct FileLayer { const char* tag; bool VxaModel::*has; std::vector<double> VxaModel::*values; };
 const FileLayer file_layers[] = {
@@ -441,8 +492,12 @@ int main(int argc, char** argv)
     const std::string mode = argc > 1 ? argv[1] : "";
     try {
         if (mode == "--dominant") { check_dominant(); return 0; }
+        if (mode == "--medium" && argc >= 7) {
+            check_medium(build_vxa_files(std::vector<std::string>(argv + 6, argv + argc), std::atoi(argv[2]), false), std::atoi(argv[2]), std::atoi(argv[3]), std::atoi(argv[4]), std::atoi(argv[5]));
+            return 0;
+        }
         if (mode == "--arrays" && argc >= 4) { check_arrays(std::atoi(argv[2]), std::vector<std::string>(argv + 3, argv + argc)); return 0; }
-        if (argc < 4 || mode[0] == '-') { std::fprintf(stderr, "usage: batch_check <variant 0|1> <CUs> robot.vxa... | --arrays <variant 0|1> robot.vxa... | --dominant\n"); return 2; }
+        if (argc < 4 || mode[0] == '-') { std::fprintf(stderr, "usage: batch_check <variant 0|1> <CUs> robot.vxa... | --arrays <variant 0|1> robot.vxa... | --medium <variant 0|1> <CUs> <tiles per robot> <tile_small 0|1> robot.vxa... | --dominant\n"); return 2; }
         const int variant = std::atoi(argv[1]), n_cu = std::atoi(argv[2]);
         const Robots robots = build_vxa_files(std::vector<std::string>(argv + 3, argv + argc), variant, false);
         Options o;

@@ -140,7 +140,13 @@ enum { VXH_TILE_BLOCK = 256,          // worker threads of a tile's workgroup = 
        // the SMALL size class (round 6): tiles of at most one wavefront of owned voxels, two of mirrored ones and one bond per lane -- the 4x4x4
        // tiles of configs[4], the tiles of a swimmer above 1024 voxels -- are stepped by kernel instances whose LDS plane strides are these
        // constants instead of the tile's own counts
-       VXH_TILE_S_OWN = 64, VXH_TILE_S_HALO = 128, VXH_TILE_S_BONDS = 256 };
+       VXH_TILE_S_OWN = 64, VXH_TILE_S_HALO = 128, VXH_TILE_S_BONDS = 256,
+       // the MEDIUM size class (engine option tile_medium): tiles of at most two wavefronts of owned voxels, one mirrored voxel per lane of three
+       // wavefronts and two bonds per lane -- the 5x5x5 tiles (125 / 150 / 450) that several lattices above 1024 voxels in one batch are cut into,
+       // the tiles of tile_small shards -- with the class constants as LDS plane strides, wavefronts 0 and 1 on the voxels, 2 and 3 serving
+       VXH_TILE_M_OWN = 128, VXH_TILE_M_HALO = 192, VXH_TILE_M_BONDS = 512 };
+// size class of a robot's tiles = the instances of k_tile_steps that step them (Planned / TileLaunchPlan::cls, batch.cpp)
+enum { VXH_TILE_CLASS_GENERIC = 0, VXH_TILE_CLASS_SMALL = 1, VXH_TILE_CLASS_MEDIUM = 2 };
 struct TileLayout { int np, no, nbp, nmvp, nfp, nmxp, o_ps, o_pl, o_hl, o_pht, o_sl, o_sc, o_px, o_rc, o_tab, o_int, o_mesh, total; };
 VXH_HD inline TileLayout tile_layout(int n_own, int n_halo, int nb, int tab_doubles, bool mesh, int n_mv = 0, int n_f = 0, int n_mx = 0)
 {

@@ -401,6 +401,7 @@ const OptionDesc option_table[] = {
     {"tiled",             &Options::tiled,             OptionDesc::INT,  OptionDesc::WHOLE, 0, 2,      true,  false},
     {"tiles_per_robot",   &Options::tiles_per_robot,   OptionDesc::INT,  OptionDesc::RANGE, 0, 4096,   true,  false},
     {"tile_small",        &Options::tile_small,        OptionDesc::FLAG, OptionDesc::WHOLE, 0, 1,      true,  false},
+    {"tile_medium",       &Options::tile_medium,       OptionDesc::FLAG, OptionDesc::WHOLE, 0, 1,      true,  false},
     {"wide",              &Options::wide,              OptionDesc::FLAG, OptionDesc::WHOLE, 0, 1,      true,  false},
     {"wide_two_tiles",    &Options::wide_two_tiles,    OptionDesc::FLAG, OptionDesc::WHOLE, 0, 1,      true,  false},
     {"wide_small",        &Options::wide_small,        OptionDesc::FLAG, OptionDesc::WHOLE, 0, 1,      true,  false},
@@ -824,7 +825,7 @@ void Engine::advance_launch(long long max_rounds)
         for (long long done = 0; done < todo || done == 0; done += iters)
             for (const auto& L : D.tile_launches) {
                 ++tile_gen_;
-                launch_tile_group(B, L.tabg != 0, L.mesh, L.small != 0, L.list, L.count, L.lds, D.tile_stream, cap, iters, tile_gen_);
+                launch_tile_group(B, L.tabg != 0, L.mesh, L.cls, L.list, L.count, L.lds, D.tile_stream, cap, iters, tile_gen_);
                 ++launches; ++tile_launch_count;
             }
         HIP_OK(hipEventRecord(D.tile_t1, D.tile_stream));

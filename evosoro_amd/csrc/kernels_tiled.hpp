@@ -45,6 +45,9 @@
 // memory round trip whoever owns the voxel.  Then: vertices (corner-code order, as fused_drag and k_mesh_vertices), a workgroup barrier,
 // the facets' drag next to the bond phase, and behind barrier (B) every voxel adds its facets in the reference's order.  Same arithmetic
 // and orders as the resident / wide / streaming kernels: different tilings give the same bits (tests/test_gpu_tiled.py).
+// Size classes (template argument CLS): a launch whose tiles are all within VXH_TILE_S_* (SMALL, round 6) or within VXH_TILE_M_* (MEDIUM, engine
+// option tile_medium) runs instances laid out for the largest tile of the class, every LDS stride and offset an immediate; MEDIUM also fixes which
+// wavefronts hold voxels and which serve, and keeps every lane's bond entries in registers (at the layout, below).  Same arithmetic, same orders.
 // The control block (time, stop rule, collision horizon) is replicated: every tile runs the same serial control code on the
 // same inputs.  Residency: all tiles of a robot must be on the chip at the same time; the host sizes every launch to what the
 // CUs admit and issues the tiled launches of an engine on ONE stream.  Spins are bounded (VXH_ROBOT_SYNC_TIMEOUT).
@@ -335,11 +338,14 @@ __device__ __forceinline__ int tile_rebuild(const DBatch& B, const DRobot& R, DR
 #endif
 
 
-template <bool TABG, bool MESH, bool FLUID = false, bool SMALL = false>      // FLUID (implies MESH): the robots of the launch are in a fluid (drag mesh per tile, strains exchanged)
+// FLUID (implies MESH): the robots of the launch are in a fluid (drag mesh per tile, strains exchanged).  CLS: the size class of the launch's
+// tiles (VXH_TILE_CLASS_*, device_types.hpp) -- GENERIC takes any tile, SMALL and MEDIUM only tiles within their three bounds.
+template <bool TABG, bool MESH, bool FLUID = false, int CLS = VXH_TILE_CLASS_GENERIC>
 __global__ __launch_bounds__(VXH_TILE_THREADS) void k_tile_steps(DBatch B, const DRobot* __restrict__ robots, const DTile* __restrict__ tiles,
                                                                  const int* __restrict__ tile_list, long long step_cap, int iters, unsigned gen)
 {
     constexpr int BLOCK = VXH_TILE_BLOCK, NT = VXH_TILE_THREADS;   // worker threads (one per owned voxel), all threads
+    constexpr bool SMALL = CLS == VXH_TILE_CLASS_SMALL, MEDIUM = CLS == VXH_TILE_CLASS_MEDIUM;
     extern __shared__ __align__(16) double lds[];
     __shared__ DRobotState rs, rs_bak, rs_bak2;
     __shared__ FusedCtl s_ctl[2];
@@ -372,7 +378,16 @@ __global__ __launch_bounds__(VXH_TILE_THREADS) void k_tile_steps(DBatch B, const
     // SMALL (every tile of the launch within VXH_TILE_S_*): the layout of the LARGEST such tile for all of them -- np, no, nbp and every
     // offset in front of the class tables are compile-time constants, i.e. immediates of the LDS instructions instead of scalar registers
     // (the kernel spilled ~250 of those into VGPR lanes and read them back ~250 times per step and wavefront)
+    // MEDIUM (every tile within VXH_TILE_M_*, option tile_medium): the same with that class's constants, and a work split of its own -- at most
+    // 128 owned voxels, so wavefronts 0 and 1 hold the voxels and 2 and 3 never do (the next step's control on 2, the per-robot barrier and the
+    // horizon decision on 3: which wavefront serves is a constant, not a function of n_own); no half-voxel `split` mode (that stays SMALL's);
+    // at most one halo voxel per lane (one poll, no loop); and every lane carries its up to BPL bond entries and their classes in REGISTERS for
+    // the whole launch, evaluated in BPL unrolled rounds, instead of reading them from LDS in a loop of run-time length
+    static_assert(VXH_TILE_M_OWN <= BLOCK - 128 && VXH_TILE_M_HALO <= BLOCK && VXH_TILE_M_BONDS % BLOCK == 0, "MEDIUM: two wavefronts of voxels, one halo voxel per lane, whole bond rounds");
+    static_assert(VXH_TILE_M_OWN + VXH_TILE_M_HALO <= 1024, "packed bond entries: ten bits per end");
+    constexpr int BPL = VXH_TILE_M_BONDS / BLOCK;
     const TileLayout L = SMALL ? tile_layout(VXH_TILE_S_OWN, VXH_TILE_S_HALO, VXH_TILE_S_BONDS, nbd + nvd, MESH, n_mv, n_f, n_mx)
+                       : MEDIUM ? tile_layout(VXH_TILE_M_OWN, VXH_TILE_M_HALO, VXH_TILE_M_BONDS, nbd + nvd, MESH, n_mv, n_f, n_mx)
                                : tile_layout(n_own, n_halo, nb, nbd + nvd, MESH, n_mv, n_f, n_mx);
     const int np = L.np, no = L.no, nbp = L.nbp;
     double* const ps = lds + L.o_ps;          // [8][np] pose tile: owned voxels, then halo voxels
@@ -484,7 +499,7 @@ __global__ __launch_bounds__(VXH_TILE_THREADS) void k_tile_steps(DBatch B, const
     // the two halves never read each other's results within a step (voxel_update is one behind the other: same operations, same bits) and
     // each keeps its momentum in registers and publishes its part of the pose.  (Round 3 measured this split slower -- with 236-368 bytes of
     // scratch per lane, whose reloads queued behind the publication's write-through stores; the kernel has no scratch any more.)
-    const bool split = n_own <= 64;
+    const bool split = !MEDIUM && n_own <= 64;
     const int av = split ? tid - 64 : tid;                         // the voxel whose rotation half this thread runs
     const bool do_ang = split ? (tid >= 64 && av < n_own) : valid;
     const int gva = do_ang ? (split ? B.tile_vox[T.vox_off + av] : gv) : R.vox_begin;
@@ -500,7 +515,13 @@ __global__ __launch_bounds__(VXH_TILE_THREADS) void k_tile_steps(DBatch B, const
     const int hv0 = hslot0 < n_halo ? B.tile_vox[T.vox_off + n_own + hslot0] : 0;      // my (first) halo voxel: its exchange slot
     __syncthreads();
     const int nvw = (n_own + 63) >> 6;        // wavefronts that hold voxels
-    const int ctl0 = n_own <= SVC0 - 64 ? SVC0 - 64 : SVC0;
+    const int ctl0 = MEDIUM || n_own <= SVC0 - 64 ? SVC0 - 64 : SVC0;
+    // MEDIUM: my bond entries and their classes (-1: none), out of the LDS tables filled above
+    int my_be[BPL], my_bc[BPL];
+    if constexpr (MEDIUM) {
+#pragma unroll
+        for (int j = 0; j < BPL; ++j) { const int b = tid + j * BLOCK; my_be[j] = b < nb ? bent[b] : -1; my_bc[j] = b < nb ? bcls[b] : 0; }
+    }
     const bool ctl_wave = (tid & ~63) == ctl0, ctl_thread = tid == ctl0;      // the wavefront of the next step's control, its first lane
     const bool hz_thread = tid == SVC0;       // the lane that takes the horizon decision: first of the wavefront that resolves the per-robot barrier
     // snapshots of the control block by the whole control wavefront, a dword per lane (one LDS round trip instead of ten on one lane)
@@ -663,6 +684,7 @@ __global__ __launch_bounds__(VXH_TILE_THREADS) void k_tile_steps(DBatch B, const
                 }
 #pragma unroll
                 for (int k = 0; k < 8; ++k) ps[k * np + n_own + h] = gran2_value(g[2 * k], g[2 * k + 1]);
+                if constexpr (MEDIUM) break;   // (n_halo <= BLOCK: one halo voxel per lane)
             }
             // ... and the contact partners the tile mirrors (position + scale: 8 granules), same protocol
             for (int e = hslot0; e < s_xhn; e += BLOCK) {
@@ -760,8 +782,11 @@ __global__ __launch_bounds__(VXH_TILE_THREADS) void k_tile_steps(DBatch B, const
                     }
                 }
             }
-            for (int b = tid; b < nb; b += BLOCK) {
-                const int e = bent[b];
+            // (MEDIUM: BPL unrolled rounds on the entries the lane carries; else a loop of run-time length over the LDS tables)
+#pragma unroll(MEDIUM ? BPL : 1)
+            for (int b = tid, j = 0; MEDIUM ? j < BPL : b < nb; b += BLOCK, ++j) {
+                if (MEDIUM && my_be[j] < 0) break;
+                const int e = MEDIUM ? my_be[j] : bent[b];
                 const int l1 = e & 1023, l2 = (e >> 10) & 1023, axis = (e >> 20) & 3;
                 BondHist H;
                 H.p0 = hl[b]; H.p1 = hl[nbp + b]; H.p2 = hl[2 * nbp + b]; H.g0 = hl[3 * nbp + b]; H.g1 = hl[4 * nbp + b]; H.g2 = hl[5 * nbp + b];
@@ -773,7 +798,7 @@ __global__ __launch_bounds__(VXH_TILE_THREADS) void k_tile_steps(DBatch B, const
                 const d3 p2 = mk3(ps[l2], ps[np + l2], ps[2 * np + l2]);
                 const double s2 = ps[3 * np + l2];
                 const dq q2 = mkq(ps[4 * np + l2], ps[5 * np + l2], ps[6 * np + l2], ps[7 * np + l2]);
-                const BondOut o = bond_compute_rt(axis, B, bct[bcls[b]], H, p1, q1, s1, p2, q2, s2, damp_on);
+                const BondOut o = bond_compute_rt(axis, B, bct[MEDIUM ? my_bc[j] : bcls[b]], H, p1, q1, s1, p2, q2, s2, damp_on);
                 if (H.store_hist) { hl[b] = H.p0; hl[nbp + b] = H.p1; hl[2 * nbp + b] = H.p2; hl[3 * nbp + b] = H.g0; hl[4 * nbp + b] = H.g1; hl[5 * nbp + b] = H.g2; }
                 hf[b] = (int)H.flags;
                 div = div || o.diverged;

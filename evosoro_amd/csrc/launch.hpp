@@ -39,9 +39,10 @@ void launch_fused_mesh(const DBatch& B, int block, bool tabg, const int* list, i
 // k_robot_wide<block, MESH, TABG, STATS> (kernels_wide.hpp); block: 512, or VXH_WIDE_SMALL_BLOCK for a group of small robots (option wide_small);
 // stats (with launch_fused_land too): the STATS instances, for groups of robots under StopConditionType 4-7 (512 only)
 void launch_wide_group(const DBatch& B, int block, bool mesh, bool tabg, bool stats, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters, int two_tiles);
-// k_tile_steps<TABG, MESH, FLUID> (kernels_tiled.hpp); mesh_kind: 0 = _voxcad, 1 = land_water robot on land, 2 = in a fluid
-// small: every tile of the launch within VXH_TILE_S_OWN / _HALO / _BONDS (device_types.hpp): the instances with compile-time LDS strides
-void launch_tile_group(const DBatch& B, bool tabg, int mesh_kind, bool small, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters, unsigned gen);
+// k_tile_steps<TABG, MESH, FLUID, CLS> (kernels_tiled.hpp); mesh_kind: 0 = _voxcad, 1 = land_water robot on land, 2 = in a fluid
+// cls: VXH_TILE_CLASS_* (device_types.hpp) -- SMALL / MEDIUM: every tile of the launch within VXH_TILE_S_* / VXH_TILE_M_*: the instances with
+// compile-time LDS strides
+void launch_tile_group(const DBatch& B, bool tabg, int mesh_kind, int cls, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters, unsigned gen);
 // threads of a tile's workgroup (the host sizes launches and LDS with the kernel's own constants)
 int tile_threads();
 // the streaming kernels (kernels_stream.hpp).  One time step of the streamed robots: k_step_begin, k_mesh_vertices and k_facets when any robot is

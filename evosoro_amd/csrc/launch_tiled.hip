@@ -8,7 +8,7 @@
 namespace vxh {
 
 // (one table of granted dynamic-LDS sizes per kernel instance: the limit only ever grows)
-template <bool TABG, bool MESH, bool FLUID, bool SMALL>
+template <bool TABG, bool MESH, bool FLUID, int CLS>
 static size_t (&granted_lds())[64] { static size_t table[64] = {}; return table; }
 
 // k_tile_steps must keep NOTHING in scratch (round 6).  Its tiles exchange poses through relaxed agent-scope stores and polled loads, and
@@ -20,7 +20,7 @@ static size_t (&granted_lds())[64] { static size_t table[64] = {}; return table;
 // "Round 6").  Four wavefronts per workgroup leave every wavefront 512 registers, the compiler spills into the upper 256 (AGPRs), and
 // this check keeps it that way: a build that needs scratch again is refused with VXH_ERR_HIP before it is launched.
 // (VXH_TILE_SCRATCH_LIMIT: bytes per lane tolerated, default 0; the GPU test sets -1 to see the refusal.)
-template <bool TABG, bool MESH, bool FLUID, bool SMALL>
+template <bool TABG, bool MESH, bool FLUID, int CLS>
 static void refuse_scratch()
 {
     static std::mutex lock;
@@ -34,7 +34,7 @@ static void refuse_scratch()
         std::lock_guard<std::mutex> hold(lock);
         if (!known[dev]) {
             hipFuncAttributes attr;
-            hip_check(hipFuncGetAttributes(&attr, (const void*)k_tile_steps<TABG, MESH, FLUID, SMALL>), "hipFuncGetAttributes(k_tile_steps)");
+            hip_check(hipFuncGetAttributes(&attr, (const void*)k_tile_steps<TABG, MESH, FLUID, CLS>), "hipFuncGetAttributes(k_tile_steps)");
             bytes[dev] = (long)attr.localSizeBytes; known[dev] = true;
         }
         have = bytes[dev];
@@ -42,31 +42,33 @@ static void refuse_scratch()
     const char* env = std::getenv("VXH_TILE_SCRATCH_LIMIT");
     const long limit = env ? std::atol(env) : 0;
     if (have > limit)
-        throw std::runtime_error("HIP: k_tile_steps<" + std::to_string((int)TABG) + ", " + std::to_string((int)MESH) + ", " + std::to_string((int)FLUID) + ", " + std::to_string((int)SMALL) + "> was compiled with " +
+        throw std::runtime_error("HIP: k_tile_steps<" + std::to_string((int)TABG) + ", " + std::to_string((int)MESH) + ", " + std::to_string((int)FLUID) + ", " + std::to_string(CLS) + "> was compiled with " +
                                  std::to_string(have) + " bytes of scratch per lane (limit " + std::to_string(limit) + "): refused, see evosoro_amd/csrc/launch_tiled.hip");
 }
 
-template <bool TABG, bool MESH, bool FLUID, bool SMALL>
+template <bool TABG, bool MESH, bool FLUID, int CLS>
 static void launch_tiles(const DBatch& B, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters, unsigned gen)
 {
-    refuse_scratch<TABG, MESH, FLUID, SMALL>();
-    grant_dynamic_lds((const void*)k_tile_steps<TABG, MESH, FLUID, SMALL>, granted_lds<TABG, MESH, FLUID, SMALL>(), lds);
-    hipLaunchKernelGGL((k_tile_steps<TABG, MESH, FLUID, SMALL>), dim3(count), dim3(VXH_TILE_THREADS), lds, s, B, B.robot, B.tiles, list, cap, iters, gen);
+    refuse_scratch<TABG, MESH, FLUID, CLS>();
+    grant_dynamic_lds((const void*)k_tile_steps<TABG, MESH, FLUID, CLS>, granted_lds<TABG, MESH, FLUID, CLS>(), lds);
+    hipLaunchKernelGGL((k_tile_steps<TABG, MESH, FLUID, CLS>), dim3(count), dim3(VXH_TILE_THREADS), lds, s, B, B.robot, B.tiles, list, cap, iters, gen);
 }
 
-template <bool SMALL>
+template <int CLS>
 static void launch_tile_group_of(const DBatch& B, bool tabg, int mesh_kind, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters, unsigned gen)
 {
-    if (mesh_kind == 2) { if (tabg) launch_tiles<true, true, true, SMALL>(B, list, count, lds, s, cap, iters, gen); else launch_tiles<false, true, true, SMALL>(B, list, count, lds, s, cap, iters, gen); }
-    else if (mesh_kind) { if (tabg) launch_tiles<true, true, false, SMALL>(B, list, count, lds, s, cap, iters, gen); else launch_tiles<false, true, false, SMALL>(B, list, count, lds, s, cap, iters, gen); }
-    else if (tabg) launch_tiles<true, false, false, SMALL>(B, list, count, lds, s, cap, iters, gen);
-    else launch_tiles<false, false, false, SMALL>(B, list, count, lds, s, cap, iters, gen);
+    if (mesh_kind == 2) { if (tabg) launch_tiles<true, true, true, CLS>(B, list, count, lds, s, cap, iters, gen); else launch_tiles<false, true, true, CLS>(B, list, count, lds, s, cap, iters, gen); }
+    else if (mesh_kind) { if (tabg) launch_tiles<true, true, false, CLS>(B, list, count, lds, s, cap, iters, gen); else launch_tiles<false, true, false, CLS>(B, list, count, lds, s, cap, iters, gen); }
+    else if (tabg) launch_tiles<true, false, false, CLS>(B, list, count, lds, s, cap, iters, gen);
+    else launch_tiles<false, false, false, CLS>(B, list, count, lds, s, cap, iters, gen);
 }
 
-void launch_tile_group(const DBatch& B, bool tabg, int mesh_kind, bool small, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters, unsigned gen)
+void launch_tile_group(const DBatch& B, bool tabg, int mesh_kind, int cls, const int* list, int count, size_t lds, hipStream_t s, long long cap, int iters, unsigned gen)
 {
-    if (small) launch_tile_group_of<true>(B, tabg, mesh_kind, list, count, lds, s, cap, iters, gen);
-    else launch_tile_group_of<false>(B, tabg, mesh_kind, list, count, lds, s, cap, iters, gen);
+    if (cls == VXH_TILE_CLASS_SMALL) launch_tile_group_of<VXH_TILE_CLASS_SMALL>(B, tabg, mesh_kind, list, count, lds, s, cap, iters, gen);
+    else if (cls == VXH_TILE_CLASS_MEDIUM) launch_tile_group_of<VXH_TILE_CLASS_MEDIUM>(B, tabg, mesh_kind, list, count, lds, s, cap, iters, gen);
+    else if (cls == VXH_TILE_CLASS_GENERIC) launch_tile_group_of<VXH_TILE_CLASS_GENERIC>(B, tabg, mesh_kind, list, count, lds, s, cap, iters, gen);
+    else throw std::runtime_error("HIP: k_tile_steps has no size class " + std::to_string(cls));
 }
 
 int tile_threads() { return VXH_TILE_THREADS; }

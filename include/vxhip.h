@@ -234,6 +234,12 @@ int  vxh_count_bond_modes(const vxh_engine* e, long long* large_angle_out, long 
  *                       (measured in round 6 on one 64-robot shard of the bench population: 14.0 us per step against 12.0 with the default
  *                       kernels -- it no longer pays there; kept for A/B), at the price that such a robot's last bits then
  *                       depend on the population it is evaluated in (the two kernels agree to 1e-12 voxel, not to the bit).  Default 0.
+ *   "tile_medium"       1 = a tiled robot whose tiles are not all within 64 owned / 128 mirrored voxels / 256 bonds but all within 128 / 192 /
+ *                       512 -- several lattices above 1024 voxels in one batch, the tiles of "tile_small" shards -- is stepped by the MEDIUM
+ *                       instances of the multi-workgroup kernel: LDS strides and offsets fixed at compile time, the voxels on two
+ *                       wavefronts, every lane's bond entries in registers.  Which class a robot takes follows from its tiles alone.  Same
+ *                       arithmetic on the same operands in the same order: the state bytes are those of 0.  Default 0 (the generic
+ *                       instances, as before); an A/B option.
  *   "tiles_per_robot"   > 0 requests a tile count (tests).
  *   "wide"              1 (default) = robots of up to 512 voxels and 1023 bonds are stepped by the wide kernel (one lane per bond, all
  *                       three axes at once, forces summed in the reference's order); 0 = by the resident kernel with its three bond
